@@ -15,7 +15,7 @@ fusion kernel, HBM), `roofline_attention`, `fp8_config3` (the same step with e4m
 `cached_questions` (scene-level reuse, SURVEY 8 f1: further questions about an already prefilled scene), `ground_config2`
 (the ScanRefer / Multi3DRefer grounding forward at 32 frames / 50 proposals, BASELINE configs[2], one GPU) and `cpu_baseline`.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (RANK / WORLD_SIZE in the
 environment), or started plainly - then THIS process, before it touches the GPU, starts exactly that command as a child (one rank
@@ -516,6 +516,15 @@ def measure_train_step(dev, steps=2, answer_tokens=64):
                           "ms_forward_backward": rc_ms[-1], "peak_mem_gb": rc_peak}}
 
 
+def dump_outputs(out_dir, token_rows):
+    """--dump-outputs DIR: what the timed pipeline returned to its caller - the new token ids of every timed (scene, question), in
+    question order, one row per step (the last row is the last step) - as DIR/answer_token_ids.npy in float64 (exact for token ids).
+    Inputs and weights are seeded, so two builds run with the same arguments can be compared array for array."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "answer_token_ids.npy"), np.asarray(token_rows, dtype=np.float64))
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` with N > 1 and no launcher environment: start `torch.distributed.run` with N ranks of this very file as a
     CHILD process (never an exec, and before this process has made any GPU call), let rank 0's JSON line through and return the child's
@@ -553,6 +562,8 @@ def dry_run(a, rank, world):
         if multi:
             assert [r["sample_id"] for r in merged] == list(range(world * a.steps)), "gathered records are not in question order"
             assert all(r["pred_token_ids"] == [(7 * r["sample_id"] + k) % 1000 for k in range(NEW_TOKENS)] for r in merged)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, [r["pred_token_ids"] for r in merged] if multi else answers)
         print(json.dumps({"metric": "scenes/sec ScanQA @32 frames", "value": world * a.steps / dt_s, "unit": "scenes/s", "n_gpus": world,
                           "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt_s / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
                           "vs_baseline": None, "dtype": "bf16", "data": "DRY RUN (V3D_BENCH_DRY=1): no GPU, a stand-in for the scene pipeline - not a measurement",
@@ -578,6 +589,8 @@ def main():
     ap.add_argument("--prefill-streams", type=int, default=2, help="streams that prefill consecutive scenes side by side (each with its own scratch)")
     ap.add_argument("--eval-runner-only", action="store_true", help="after the headline run only the eval_runner extra (development)")
     ap.add_argument("--scenes", type=int, default=8, help="distinct synthetic scenes resident in HBM, cycled over the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline run's answer token ids to DIR/answer_token_ids.npy (float64)")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
@@ -640,7 +653,7 @@ def main():
     def measure(eng, stamps):
         """W untimed warm-up scenes, then EXACTLY `steps` scenes between barrier + synchronize; max over ranks.  The timed region IS the
         product's scene pipeline (v3d.pipeline.ScenePipeline.run - the eval runners call the same function): prefill per scene on stream A,
-        decode groups on stream B, two context sets."""
+        decode groups on stream B, two context sets.  -> (seconds, the answer token rows of all ranks in question order on rank 0)."""
         pipe = ScenePipeline(eng, G_ALL, prefill_streams=a.prefill_streams)
         if a.warmup:
             pipe.run(samples_of(scenes, max(a.warmup, min(G_ALL, a.steps)), SceneSample), NEW_TOKENS, overlap=not a.no_overlap, trim=False)
@@ -661,9 +674,12 @@ def main():
                 assert [r["sample_id"] for r in merged] == list(range(world * a.steps)), "gathered records are not in question order"
         assert answers.shape == (a.steps, NEW_TOKENS)
         eng.use(pipe.sets[0][0])
-        return dt_s
+        rows = [r["pred_token_ids"] for r in merged] if multi and rank == 0 else answers.tolist()
+        return dt_s, rows
 
-    dt_s = measure(eng, stamps)
+    dt_s, rows = measure(eng, stamps)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, rows)
     extras = {}
     if world == 1 and not a.no_extras and not a.eval_runner_only:
         # BASELINE.json's stated synthetic proxy (a 4096-token sequence; SURVEY 8(d) asks for it NEXT to the true shape).  No frame count
@@ -673,7 +689,7 @@ def main():
         keep_scenes = scenes
         scenes = [synth_inputs(dev, dtype, seed=2000 + i, frames=PF, text_post=PPOST) for i in range(min(4, n_scenes))]
         st4 = new_stamps()
-        t4 = measure(eng, st4)
+        t4, _ = measure(eng, st4)
         scenes = keep_scenes
         a_us = st4["attn"].mean_us()
         extras["s4096_proxy"] = {
@@ -711,7 +727,7 @@ def main():
             torch.cuda.empty_cache()
             eng8 = Engine(cfg, sd, dtype=dtype, device=dev, max_frames=FRAMES, llm_fp8=True)
             st8 = new_stamps()
-            t8 = measure(eng8, st8)
+            t8, _ = measure(eng8, st8)
             g8 = st8["gemm"].mean_us()
             extras["fp8_config3"] = {
                 "what": "BASELINE configs[3]: same scene step with e4m3 (per-row scaled) weights in the Qwen2 linears and LM head "

@@ -127,6 +127,19 @@ def test_bench_launches_its_own_ranks_when_started_plainly():
     assert "torch.distributed.run" in r.stderr and "--nproc-per-node=2" in r.stderr
 
 
+def test_bench_dump_outputs_writes_the_answer_rows_in_question_order(tmp_path):
+    """--dump-outputs DIR: after the timed steps, the answer token ids of every timed step (one row each, question order, gathered over
+    the ranks) land in DIR/answer_token_ids.npy as float64; one rank and two ranks write the same array."""
+    import numpy as np
+    want = np.array([[(7 * sid + k) % 1000 for k in range(17)] for sid in range(6)], np.float64)      # dry run's stand-in answers
+    for n in (1, 2):
+        out = tmp_path / f"n{n}"
+        r = _run_bench("--gpus", str(n), "--steps", str(6 // n), "--warmup", "0", "--dump-outputs", str(out))
+        assert r.returncode == 0, r.stderr[-2000:]
+        got = np.load(out / "answer_token_ids.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, want)
+
+
 def test_bench_relays_a_failed_childs_exit_code():
     """A rank that dies takes the run down with a non-zero exit and no result line (no retry)."""
     r = _run_bench("--gpus", "2", "--steps", "3", env_extra={"V3D_BENCH_DRY_FAIL_RANK": "1"})

@@ -3,8 +3,7 @@ config.json with model_type llava_qwen, a tokenizer) is loaded with exactly the 
 (llava/model/builder.py:206-228, 266-292: AutoTokenizer, LlavaQwenConfig.from_pretrained + overwrite_config,
 LlavaQwenForCausalLM.from_pretrained(path, low_cpu_mem_usage=True, attn_implementation=..., config=..., device_map="auto",
 torch_dtype=float16), resize_token_embeddings, get_vision_tower().is_loaded / image_processor) - the reference checkout
-itself does not exist on the GPU box, so the call sequence is restated here; tests/test_overlay_loader.py runs the real
-builder.py over the overlay in the build container.  The weights are those of tests/golden/tiny_model.npz, so generate /
+is not part of this repository, so the call sequence is restated here.  The weights are those of tests/golden/tiny_model.npz, so generate /
 forward are compared with the REFERENCE model's own outputs."""
 import os
 
