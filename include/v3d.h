@@ -517,6 +517,21 @@ int v3d_ground_infonce(const void* obj, int64_t ldo, int n, const void* query, i
 int v3d_masked_mean_grad(const uint8_t* mask, int n_obj, int T, int C, const void* dobj, void* dfeat, int accumulate, float* inv_count,
                          int dtype, void* stream);
 
+/* The grounding loss of the 'mlp' and 'score' heads (llava_qwen.py:283-293, 313-322), the heads' score tail and its backward in one
+ * launch: s_i = sum_c x[i,c] w[c] (+ bias[0]; products_rounded != 0: every product rounded to the dtype first, as v3d_row_dots),
+ * with t_i = positive[i] != 0 and weight_i = t_i ? pos_weight : 1, loss = mean_i weight_i (max(s_i,0) - s_i t_i + log1p(e^-|s_i|))
+ * (BCEWithLogitsLoss(reduction='none') * weight, .mean(); f32 inside).  Writes loss (f32 scalar), scores (f32 [n], may be null),
+ * dx [n, C] = ds (x) w, dw [C] = sum_i ds_i x[i,:], dbias [1] = sum_i ds_i (may be null), ds_i = weight_i (sigmoid(s_i) - t_i) / n.
+ * pos_weight is the host's (n - P) / P of the P listed labels (ground_bce_targets).  One workgroup, sums in a fixed order (two calls
+ * give identical bits).  1 <= n <= 1024, C a multiple of 8 up to 3584, rows 16-byte aligned, dx distinct from x. */
+int v3d_ground_rowdot_bce(const void* x, int64_t ldx, int n, const void* w, int C, const void* bias, int products_rounded,
+                          const uint8_t* positive, float pos_weight, float* loss, float* scores, void* dx, int64_t lddx, void* dw,
+                          void* dbias, int dtype, void* stream);
+/* Backward of m = o * q_row (v3d_relu_mul_rows with a row, relu 0; `obj_feat * query_feat`, llava_qwen.py:290): dout[i,:] = dm[i,:] * q
+ * (one rounding), dq[c] = sum_i dm[i,c] o[i,c] in f32, rows in order.  C a multiple of 8, rows 16-byte aligned. */
+int v3d_mul_rows_grad(const void* dm, int64_t lddm, const void* o, int64_t ldo, const void* q, int n, int C, void* dout, int64_t lddo,
+                      void* dq, int dtype, void* stream);
+
 /* ------------------------------------------------------------------ host helpers -------- */
 
 /* The launch plan v3d_gemm takes for an M x N x K product on a chip with `slots` compute units (pure host code, no device needed;

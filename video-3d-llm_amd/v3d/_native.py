@@ -116,6 +116,8 @@ SIGNATURES = {
     "v3d_sumsq": (c_i, [c_p, c_l, c_i, c_p, c_i, c_p, c_p]),
     "v3d_ground_infonce": (c_i, [c_p, c_l, c_i, c_p, c_i, c_p, c_f, c_p, c_p, c_p, c_l, c_p, c_i, c_p]),
     "v3d_masked_mean_grad": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_i, c_p]),
+    "v3d_ground_rowdot_bce": (c_i, [c_p, c_l, c_i, c_p, c_i, c_p, c_i, c_p, c_f, c_p, c_p, c_p, c_l, c_p, c_p, c_i, c_p]),
+    "v3d_mul_rows_grad": (c_i, [c_p, c_l, c_p, c_l, c_p, c_i, c_i, c_p, c_l, c_p, c_i, c_p]),
     "v3d_uniform_frame_indices_host": (c_i, [c_i, c_i, c_p]),
     "v3d_gemm_plan_host": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
     "v3d_voxel_keys_f32": (c_i, [c_p, c_l, c_f, c_p, c_p]),

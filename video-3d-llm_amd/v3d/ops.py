@@ -1080,3 +1080,36 @@ def masked_mean_grad(mask, dobj, dfeat, accumulate=True):
     check(lib().v3d_masked_mean_grad(_p(mask), n, T_, C, _p(dobj), _p(dfeat), 1 if accumulate else 0, _p(inv), _code(dobj), _stream()),
           "v3d_masked_mean_grad")
     return dfeat
+
+
+def ground_rowdot_bce(x, w, positive, pos_weight, bias=None, products_rounded=False):
+    """The 'mlp' / 'score' grounding loss over the head's score tail s_i = x[i] . w (+ bias): BCE with logits against positive (device
+    uint8 [n]), positives weighted by pos_weight (ground_bce_targets), mean over the n rows.  x [n, C], w [C], bias [1] or None.
+    Returns (loss f32 scalar tensor, scores f32 [n], dx [n, C], dw [C], dbias [1] or None)."""
+    x, w = _dev(x, "x"), _dev(w, "w")
+    if x.dim() != 2:
+        raise V3DError(f"ground_rowdot_bce: x must be [n, C], got {tuple(x.shape)}")
+    n, C = x.shape
+    if w.numel() != C or w.dtype != x.dtype or (bias is not None and (bias.numel() != 1 or bias.dtype != x.dtype or not bias.is_cuda)):
+        raise V3DError(f"ground_rowdot_bce: x {tuple(x.shape)} against w {tuple(w.shape)} (and a one-element bias of x's dtype)")
+    if positive.dtype != torch.uint8 or positive.numel() != n or not positive.is_cuda or not positive.is_contiguous():
+        raise V3DError("ground_rowdot_bce: positive must be a contiguous device uint8 tensor with one entry per row")
+    loss = torch.empty(1, dtype=torch.float32, device=x.device)
+    scores = torch.empty(n, dtype=torch.float32, device=x.device)
+    dx, dw = torch.empty_like(x), torch.empty_like(w.view(-1))
+    db = torch.empty(1, dtype=x.dtype, device=x.device) if bias is not None else None
+    check(lib().v3d_ground_rowdot_bce(_p(x), x.stride(0), n, _p(w), C, _p(bias), int(bool(products_rounded)), _p(positive), float(pos_weight),
+                                      _p(loss), _p(scores), _p(dx), dx.stride(0), _p(dw), _p(db), _code(x), _stream()), "v3d_ground_rowdot_bce")
+    return loss[0], scores, dx, dw, db
+
+
+def mul_rows_grad(dm, o, q):
+    """Backward of m = o * q (q one row broadcast over o [n, C], relu_mul_rows with a row): returns (do [n, C], dq [C])."""
+    dm, o, q = _dev(dm, "dm"), _dev(o, "o"), _dev(q, "q")
+    if o.dim() != 2 or dm.shape != o.shape or q.numel() != o.shape[1] or dm.dtype != o.dtype or q.dtype != o.dtype:
+        raise V3DError(f"mul_rows_grad: dm {tuple(dm.shape)}, o {tuple(o.shape)}, q {tuple(q.shape)}")
+    n, C = o.shape
+    do, dq = torch.empty_like(o), torch.empty(C, dtype=o.dtype, device=o.device)
+    check(lib().v3d_mul_rows_grad(_p(dm), dm.stride(0), _p(o), o.stride(0), _p(q), n, C, _p(do), do.stride(0), _p(dq), _code(o), _stream()),
+          "v3d_mul_rows_grad")
+    return do, dq

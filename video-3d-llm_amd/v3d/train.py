@@ -19,8 +19,9 @@ Attention backward exists in two forms: tiled kernels that recompute the probabi
 write an [S, S] matrix (v3d_attention_backward, csrc/attention_bwd.hip - the default), and the first, MATERIALISED form below
 (one head's probability matrix in HBM with the rounding points of the reference's eager attention, modeling_qwen2.py:248-327, all five
 products on v3d_gemm), kept as an independent cross-check.  Parity: tests/test_gpu_train_dense.py, tests/test_gpu_zero2.py (autograd in
-f32 over the reference's formulae).  ground_sample_forward_backward is the grounding samples' step (infonce loss over object proposals).
-Not here: the other grounding head types, LoRA, the HF Trainer surface."""
+f32 over the reference's formulae).  ground_sample_forward_backward is the grounding samples' step over object proposals, for all three
+head types of llava_qwen.py:57-110: 'infonce' (the shipped checkpoints' loss), 'mlp' and 'score' (BCE with positive weighting, :313-322).
+Not here: LoRA; the HF Trainer surface is v3d.train_module."""
 import math
 import os
 
@@ -785,8 +786,71 @@ def _ground_head_backward(dout, saved, hp):
     return dx, {"w0": d_w0, "b0": d_b0, "ln_w": d_lnw, "ln_b": d_lnb, "w3": d_w3, "b3": d_b3}
 
 
+def _ground_head_ln_relu_forward(x, hp, last=True):
+    """ground_head_obj / ground_head_query / ground_head_score of the 'score' head (llava_qwen.py:72-91): Linear, LayerNorm (eps 1e-5),
+    ReLU, Linear - the LayerNorm BEFORE the ReLU.  last=False stops after the ReLU (the scoring MLP's Linear(1024, 1) is the row dot of
+    ground_rowdot_bce)."""
+    h = ops.gemm(x, hp["w0"], bias=hp["b0"], epilogue=ops.EPI_BIAS)
+    hn = ops.relu_mul_rows(ops.layernorm(h, hp["ln_w"], hp["ln_b"], 1e-5))
+    out = ops.gemm(hn, hp["w3"], bias=hp["b3"], epilogue=ops.EPI_BIAS) if last else hn
+    return out, (x, h, hn)
+
+
+def _ground_head_ln_relu_backward(dout, saved, hp, last=True, d_w3=None, d_b3=None):
+    """Gradients of _ground_head_ln_relu_forward; last=False: dout is the gradient of the ReLU's output and d_w3 / d_b3 (the score tail's,
+    from ground_rowdot_bce) are passed through into the tree."""
+    x, h, hn = saved
+    if last:
+        dhn, d_w3, d_b3 = linear_backward(hn, hp["w3"], dout, need_db=True)
+    else:
+        dhn = dout
+    dln = ops.gelu_grad(hn, dhn, tanh_form=2)                                    # ReLU: hn > 0 iff the LayerNorm's output was
+    dh, d_lnw, d_lnb = ops.layernorm_grad(h, hp["ln_w"], dln, 1e-5)
+    dx, d_w0, d_b0 = linear_backward(x, hp["w0"], dh, need_db=True)
+    return dx, {"w0": d_w0, "b0": d_b0, "ln_w": d_lnw, "ln_b": d_lnb, "w3": d_w3, "b3": d_b3}
+
+
+GROUND_HEAD_TYPES = ("infonce", "mlp", "score")
+
+
+def ground_bce_targets(box_labels, n):
+    """The targets of the 'mlp' / 'score' loss (llava_qwen.py:313-322) from box_labels[0] (the listed positive proposals) for n proposals:
+    (positive uint8 [n] on the host, pos_weight).  target_i = 1 for the listed i (a duplicate sets it once); weight 1, and for the
+    positives (n - P) / P with P = len(box_labels) counting duplicates.  P = 0: no positive, every weight 1; P = n: weight 0."""
+    labels = [int(i) for i in box_labels]
+    if any(i < -n or i >= n for i in labels):
+        raise V3DError(f"ground_bce_targets: a box label of {labels} is outside the {n} proposals")
+    positive = torch.zeros(n, dtype=torch.uint8)
+    if labels:
+        positive[torch.tensor(labels, dtype=torch.int64)] = 1
+    P = len(labels)
+    return positive, ((n - P) / P if P else 1.0)
+
+
+def _bce_head_forward_backward(head_type, gp, obj_feat, query_in, positive, pos_weight):
+    """The 'mlp' / 'score' head on the object features [n, H] and the normed <ground> row [1, H] (llava_qwen.py:283-293), the BCE loss and
+    the backward to both inputs.  Returns (loss, scores f32 [n], d obj_feat, d query_in, the head gradients in gp's tree)."""
+    if head_type == "mlp":
+        q_out, qsaved = _ground_head_forward(query_in, gp["head"])
+        loss, scores, d_of, d_q, _ = ops.ground_rowdot_bce(obj_feat, q_out[0], positive, pos_weight, products_rounded=True)
+        d_qin, g_head = _ground_head_backward(d_q[None], qsaved, gp["head"])
+        return loss, scores, d_of, d_qin, {"head": g_head}
+    obj_out, osaved = _ground_head_ln_relu_forward(obj_feat, gp["obj"])
+    q_out, qsaved = _ground_head_ln_relu_forward(query_in, gp["query"])
+    m = ops.relu_mul_rows(obj_out.clone(), row=q_out[0].contiguous(), relu=False)          # obj_feat * query_feat
+    hn, ssaved = _ground_head_ln_relu_forward(m, gp["score"], last=False)
+    sp = gp["score"]
+    loss, scores, d_hn, d_w3, d_b3 = ops.ground_rowdot_bce(hn, sp["w3"].view(-1), positive, pos_weight, bias=sp["b3"])
+    d_m, g_score = _ground_head_ln_relu_backward(d_hn, ssaved, sp, last=False, d_w3=d_w3.view(sp["w3"].shape), d_b3=d_b3.view(sp["b3"].shape))
+    d_obj_out, d_q_out = ops.mul_rows_grad(d_m, obj_out, q_out[0])
+    d_of, g_obj = _ground_head_ln_relu_backward(d_obj_out, osaved, gp["obj"])
+    d_qin, g_query = _ground_head_ln_relu_backward(d_q_out[None], qsaved, gp["query"])
+    return loss, scores, d_of, d_qin, {"obj": g_obj, "query": g_query, "score": g_score}
+
+
 def ground_sample_forward_backward(params, patches, voxel_ids, pe_table, pre_ids, post_ids, ground_row, obj_mask, box_pe, positive, rope, frames,
-                                   n_q, n_kv, hd, temperature=0.07, tokens=729, side=27, n=14, eps=1e-6, recompute=False):
+                                   n_q, n_kv, hd, temperature=0.07, tokens=729, side=27, n=14, eps=1e-6, recompute=False, head_type="infonce",
+                                   pos_weight=None):
     """A grounding sample of the joint training (llava_qwen.py:121-160 -> predict_box :239-310, object features llava_arch.py:351-376,
     479-501): the same tower -> projector -> splice -> decoder as sample_forward_backward, but the loss is the infonce loss between the
     <ground> token's final hidden state and the object proposals' features (masked means of the projector's patch rows + the box-centre
@@ -794,7 +858,15 @@ def ground_sample_forward_backward(params, patches, voxel_ids, pe_table, pre_ids
     uint8 [n_obj, frames * tokens] (v3d_object_patch_mask); box_pe [n_obj, H] (sin3d PE of the discretised box centres: no gradient);
     positive uint8 [n_obj + 1] (the last entry = the zero-target, set when the sample has no target box).
     params additionally holds "ground": {"obj": head, "query": head, "zero_target" [H]} (head = {w0, b0, ln_w, ln_b, w3, b3}).
-    Returns (loss, scores f32 [n_obj + 1], grads) - grads["llm"] has no "lm_head" entry (the LM head takes no part)."""
+    head_type 'mlp' / 'score' (llava_qwen.py:283-293, 313-322): the BCE loss; positive uint8 [n_obj] and pos_weight as ground_bce_targets
+    gives them (no zero-target row); "ground" holds {"head": head} ('mlp': Linear, ReLU, LayerNorm, Linear on the query, its output dotted
+    with the raw object features) or {"obj", "query", "score": head} ('score': Linear, LayerNorm, ReLU, Linear; the scoring head's w3 is
+    [1, 1024], b3 [1]).
+    Returns (loss, scores f32 [n_obj + 1] ('infonce') or [n_obj], grads) - grads["llm"] has no "lm_head" entry (the LM head takes no part)."""
+    if head_type not in GROUND_HEAD_TYPES:
+        raise V3DError(f"ground_sample_forward_backward: head_type {head_type!r}, the reference has {GROUND_HEAD_TYPES}")
+    if head_type != "infonce" and pos_weight is None:
+        raise V3DError("ground_sample_forward_backward: the BCE heads need pos_weight (ground_bce_targets)")
     with _wgrad_overlap(patches.device):
         feat, vsaved = siglip_tower_forward(patches, params["vision"], frames, tokens, recompute)
         pj, gp = params["projector"], params["ground"]
@@ -806,13 +878,18 @@ def ground_sample_forward_backward(params, patches, voxel_ids, pe_table, pre_ids
         hq = h[ground_row:ground_row + 1]
         query_in = ops.rmsnorm(hq, params["llm"]["norm"], eps)
         obj_feat = ops.masked_mean(y, obj_mask, add=box_pe)
-        of = torch.cat([obj_feat, gp["zero_target"][None].to(obj_feat.dtype)], 0).contiguous()
-        obj_out, osaved = _ground_head_forward(of, gp["obj"])
-        q_out, qsaved = _ground_head_forward(query_in, gp["query"])
-        loss, scores, d_obj_out, d_q_out = ops.ground_infonce(obj_out, q_out[0], positive, temperature)
-        # backward
-        d_of, g_obj = _ground_head_backward(d_obj_out, osaved, gp["obj"])
-        d_qin, g_query = _ground_head_backward(d_q_out[None].contiguous(), qsaved, gp["query"])
+        if head_type == "infonce":
+            of = torch.cat([obj_feat, gp["zero_target"][None].to(obj_feat.dtype)], 0).contiguous()
+            obj_out, osaved = _ground_head_forward(of, gp["obj"])
+            q_out, qsaved = _ground_head_forward(query_in, gp["query"])
+            loss, scores, d_obj_out, d_q_out = ops.ground_infonce(obj_out, q_out[0], positive, temperature)
+            # backward
+            d_of, g_obj = _ground_head_backward(d_obj_out, osaved, gp["obj"])
+            d_qin, g_query = _ground_head_backward(d_q_out[None].contiguous(), qsaved, gp["query"])
+            d_obj_feat = d_of[:-1]
+            g_ground = {"obj": g_obj, "query": g_query, "zero_target": d_of[-1].contiguous()}
+        else:
+            loss, scores, d_obj_feat, d_qin, g_ground = _bce_head_forward_backward(head_type, gp, obj_feat, query_in, positive, pos_weight)
         d_hq, d_norm = ops.rmsnorm_grad(hq, params["llm"]["norm"], d_qin, eps)
         dh = torch.zeros_like(h)
         ops.copy_rows(d_hq, dh[ground_row:ground_row + 1])
@@ -821,9 +898,8 @@ def ground_sample_forward_backward(params, patches, voxel_ids, pe_table, pre_ids
         text_rows = torch.cat([torch.arange(n_pre, device=x.device), torch.arange(n_pre + n_vis, x.shape[0], device=x.device)])
         dfeat, d_newline = inputs_embeds_backward(dx, n_pre, frames, text_rows, torch.cat([pre_ids, post_ids]), d_embed, side=side, n=n)
         dy = dfeat.view(frames * tokens, H)
-        ops.masked_mean_grad(obj_mask, d_of[:-1].contiguous(), dy, accumulate=True)       # the object features' share of the projector rows' gradient
+        ops.masked_mean_grad(obj_mask, d_obj_feat.contiguous(), dy, accumulate=True)      # the object features' share of the projector rows' gradient
         dfeat_in, pgrads = projector_backward(dy, psaved, pj["w1"], pj["w2"])
         vgrads = siglip_tower_backward(dfeat_in, vsaved, params["vision"], frames, tokens)
         return loss, scores, {"vision": vgrads, "projector": pgrads, "newline": d_newline, "embed": d_embed,
-                              "llm": {"layers": layer_grads, "norm": d_norm},
-                              "ground": {"obj": g_obj, "query": g_query, "zero_target": d_of[-1].contiguous()}}
+                              "llm": {"layers": layer_grads, "norm": d_norm}, "ground": g_ground}

@@ -11,8 +11,12 @@ forward + backward (`train.sample_forward_backward`, every operation a C-ABI cal
 checkpoint's keys (`model.layers.N.self_attn.q_proj.weight`, `model.vision_tower...`, `model.mm_projector.{0,2}`, ...) and the training
 layouts, exactly (the padding is zeros and is dropped on the way back).
 
-One sample per call, as the reference trains (`per_device_train_batch_size 1`, train_multi.sh:58).  Not here: DeepSpeed's engine, LoRA,
-the `mlp` / `score` grounding heads.
+Grounding samples (ScanRefer / Multi3DRefer): built with `ground_head_type` ('infonce', 'mlp' or 'score', the reference's
+`config.ground_head_type`, llava_qwen.py:57-110), the module also models that head's parameters under their reference keys
+(`ground_head.N.*`, `ground_head_obj/query/score.N.*`, `ground_head_zero_target`) and `forward_ground(...)` returns the grounding loss
+(`train.ground_sample_forward_backward`) with a `grad_fn`; an LM sample leaves the head's `.grad` untouched, a grounding sample the LM head's.
+
+One sample per call, as the reference trains (`per_device_train_batch_size 1`, train_multi.sh:58).  Not here: DeepSpeed's engine, LoRA.
 """
 import torch
 import torch.nn as nn
@@ -22,6 +26,26 @@ from ._native import V3DError
 from .token_ids import IGNORE_INDEX, IMAGE_TOKEN_INDEX
 
 VIT = "model.vision_tower.vision_tower.vision_model."
+
+
+# head type -> its modules: (reference prefix, key in the tree's "ground", Sequential index of the LayerNorm); Linear at 0 and 3 throughout
+_GROUND_MODULES = {"infonce": (("ground_head_obj.", "obj", 2), ("ground_head_query.", "query", 2)),      # Linear, ReLU, LayerNorm, Linear
+                   "mlp": (("ground_head.", "head", 2),),
+                   "score": (("ground_head_obj.", "obj", 1), ("ground_head_query.", "query", 1),           # Linear, LayerNorm, ReLU, Linear
+                             ("ground_head_score.", "score", 1))}
+
+
+def ground_key_map(head_type):
+    """{reference key: (module key in tree["ground"] or None, leaf)} of a grounding head type (llava_qwen.py:57-110)."""
+    if head_type not in _GROUND_MODULES:
+        raise V3DError(f"ground_head_type {head_type!r}: the reference has {tuple(_GROUND_MODULES)}")
+    out = {}
+    for pfx, mod, ln in _GROUND_MODULES[head_type]:
+        for key, leaf in (("0.weight", "w0"), ("0.bias", "b0"), (f"{ln}.weight", "ln_w"), (f"{ln}.bias", "ln_b"), ("3.weight", "w3"), ("3.bias", "b3")):
+            out[pfx + key] = (mod, leaf)
+    if head_type == "infonce":
+        out["ground_head_zero_target"] = (None, "zero_target")
+    return out
 
 
 def _flatten(tree, prefix=""):
@@ -45,10 +69,7 @@ class _SampleLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, module, args, *flat_params):
         loss, grads = train.sample_forward_backward(module.param_tree(), *args, recompute=module.recompute)
-        by_name = dict(_flatten(grads))
-        if set(by_name) != set(module.names):
-            raise V3DError("the gradient tree does not match the parameter tree")
-        ctx.grads = [by_name[n] for n in module.names]
+        ctx.grads = _match_grads(module, grads, "ground.")          # the grounding head takes no part in an LM sample
         return loss.detach().clone()
 
     @staticmethod
@@ -56,7 +77,7 @@ class _SampleLoss(torch.autograd.Function):
         scale = float(grad_loss)
         out = []
         for g in ctx.grads:
-            if scale != 1.0:
+            if g is not None and scale != 1.0:
                 if g.dtype in (torch.bfloat16, torch.float16):
                     z = torch.zeros_like(g)
                     ops.axpy(z, g.contiguous(), scale)      # 16-bit scale on the device (v3d_axpy)
@@ -68,10 +89,41 @@ class _SampleLoss(torch.autograd.Function):
         return (None, None, *out)
 
 
+def _match_grads(module, grads, absent_prefix):
+    """The gradient tree in the module's parameter order; parameters under absent_prefix (the part of the model a sample does not use)
+    may be missing and get no gradient (None: their .grad stays as it was, as under autograd)."""
+    by_name = dict(_flatten(grads))
+    missing = set(module.names) - set(by_name)
+    if set(by_name) - set(module.names) or any(not n.startswith(absent_prefix) for n in missing):
+        raise V3DError("the gradient tree does not match the parameter tree")
+    return [by_name.get(n) for n in module.names]
+
+
+class _GroundLoss(_SampleLoss):
+    """_SampleLoss for a grounding sample (train.ground_sample_forward_backward; the LM head gets no gradient)."""
+
+    @staticmethod
+    def forward(ctx, module, args, *flat_params):
+        args, kw = args
+        loss, _, grads = train.ground_sample_forward_backward(module.param_tree(), *args, recompute=module.recompute, **kw)
+        ctx.grads = _match_grads(module, grads, "llm.lm_head")
+        return loss.detach().clone()
+
+
 class LlavaQwenTrainable(nn.Module):
     def __init__(self, tree, n_q, n_kv, head_dim=128, vit_heads=16, vit_inter=4304, rope_theta=1e6, max_pos=8192, recompute=False,
-                 min_xyz=(-15, -15, -5), max_xyz=(15, 15, 5), voxel_size=0.1):
+                 min_xyz=(-15, -15, -5), max_xyz=(15, 15, 5), voxel_size=0.1, ground_head_type=None, ground_temperature=0.07,
+                 ground_token_ids=None):
+        """ground_head_type: None (no grounding head modelled) or 'infonce' / 'mlp' / 'score' with tree["ground"] in the layout of
+        train.ground_sample_forward_backward; ground_temperature: the infonce head's config.ground_head_temperature; ground_token_ids:
+        config.ground_token_ids (the label ids whose row is the grounding query, llava_qwen.py:280)."""
         super().__init__()
+        if ground_head_type is not None:
+            ground_key_map(ground_head_type)                        # a known type
+            if "ground" not in tree:
+                raise V3DError(f"ground_head_type {ground_head_type!r} but the tree has no 'ground' entry")
+        self.ground_head_type, self.ground_temperature = ground_head_type, ground_temperature
+        self.ground_token_ids = None if ground_token_ids is None else [int(i) for i in ground_token_ids]
         flat = _flatten(tree)
         self.names = [n for n, _ in flat]
         self._params = nn.ParameterList([nn.Parameter(t, requires_grad=True) for _, t in flat])
@@ -100,8 +152,9 @@ class LlavaQwenTrainable(nn.Module):
 
     # ------------------------------------------------------------------ checkpoints in the reference's keys
     @classmethod
-    def from_reference_state_dict(cls, sd, n_q, n_kv, vit_heads=16, dtype=torch.bfloat16, device="cuda", kpad=640, **kw):
-        """sd: the reference's state dict (llava_qwen.py / siglip_encoder.py / builder.py keys) -> the module."""
+    def from_reference_state_dict(cls, sd, n_q, n_kv, vit_heads=16, dtype=torch.bfloat16, device="cuda", kpad=640, ground_head_type=None, **kw):
+        """sd: the reference's state dict (llava_qwen.py / siglip_encoder.py / builder.py keys) -> the module.  ground_head_type: the
+        grounding head to model (its ground_head* keys must be in sd); None carries any ground_head* tensors through unmodelled."""
         t = lambda k: sd[k].to(device=device, dtype=dtype)       # noqa: E731
         n_vit = 1 + max(int(k[len(VIT + "encoder.layers."):].split(".")[0]) for k in sd if k.startswith(VIT + "encoder.layers."))
         n_llm = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("model.layers."))
@@ -134,19 +187,33 @@ class LlavaQwenTrainable(nn.Module):
                               "w2": t("model.mm_projector.2.weight").contiguous(), "b2": t("model.mm_projector.2.bias")},
                 "newline": t("model.image_newline"), "embed": t("model.embed_tokens.weight").contiguous(),
                 "llm": {"layers": llm_layers, "norm": t("model.norm.weight"), "lm_head": t("lm_head.weight").contiguous()}}
+        if ground_head_type is not None:
+            keys = ground_key_map(ground_head_type)
+            absent = [k for k in keys if k not in sd]
+            if absent:
+                raise V3DError(f"ground_head_type {ground_head_type!r} but the state dict has no {absent[0]}")
+            ground = {}
+            for k, (mod, leaf) in keys.items():
+                if mod is None:
+                    ground[leaf] = t(k).contiguous()
+                else:
+                    ground.setdefault(mod, {})[leaf] = t(k).contiguous()
+            tree["ground"] = ground
         hd = tree["llm"]["layers"][0]["qkv"].shape[0] // (n_q + 2 * n_kv)
-        m = cls(tree, n_q, n_kv, head_dim=hd, vit_heads=vit_heads, vit_inter=sd[VIT + "encoder.layers.0.mlp.fc1.weight"].shape[0], **kw)
+        m = cls(tree, n_q, n_kv, head_dim=hd, vit_heads=vit_heads, vit_inter=sd[VIT + "encoder.layers.0.mlp.fc1.weight"].shape[0],
+                ground_head_type=ground_head_type, **kw)
         m._patch_shape = tuple(pw.shape)
         # tensors a real LlavaQwen checkpoint holds and this module does not train - vision_model.post_layernorm (stays in the tower after
         # siglip_encoder.py:570-571), the vision_model.head.* pooling head, the ground_head* tensors, rotary inv_freq buffers, ...: kept
         # as they came (frozen, on the host) and emitted unchanged by reference_state_dict(), so that a checkpoint saved through this
         # surface loads strictly on the reference's side
-        m._passthrough = {k: v.detach().clone().cpu() for k, v in sd.items() if k not in m._modelled_keys(n_vit, n_llm)}
+        m._passthrough = {k: v.detach().clone().cpu() for k, v in sd.items() if k not in m._modelled_keys(n_vit, n_llm, ground_head_type)}
         return m
 
     @staticmethod
-    def _modelled_keys(n_vit, n_llm):
-        keys = {VIT + "embeddings.patch_embedding.weight", VIT + "embeddings.patch_embedding.bias", VIT + "embeddings.position_embedding.weight",
+    def _modelled_keys(n_vit, n_llm, ground_head_type=None):
+        keys = set(ground_key_map(ground_head_type)) if ground_head_type is not None else set()
+        keys |= {VIT + "embeddings.patch_embedding.weight", VIT + "embeddings.patch_embedding.bias", VIT + "embeddings.position_embedding.weight",
                 "model.mm_projector.0.weight", "model.mm_projector.0.bias", "model.mm_projector.2.weight", "model.mm_projector.2.bias",
                 "model.image_newline", "model.embed_tokens.weight", "model.norm.weight", "lm_head.weight"}
         for i in range(n_vit):
@@ -194,6 +261,9 @@ class LlavaQwenTrainable(nn.Module):
             out[p + "mlp.down_proj.weight"] = L["down"].clone()
             out[p + "input_layernorm.weight"], out[p + "post_attention_layernorm.weight"] = L["ln1"].clone(), L["ln2"].clone()
         out["model.norm.weight"], out["lm_head.weight"] = tr["llm"]["norm"].clone(), tr["llm"]["lm_head"].clone()
+        if self.ground_head_type is not None:
+            for k, (mod, leaf) in ground_key_map(self.ground_head_type).items():
+                out[k] = (tr["ground"][leaf] if mod is None else tr["ground"][mod][leaf]).clone()
         for k, v in getattr(self, "_passthrough", {}).items():      # unmodelled tensors of the source checkpoint, unchanged
             out[k] = v.clone()
         return out
@@ -230,3 +300,52 @@ class LlavaQwenTrainable(nn.Module):
         args = (patches, vox, self.pe_table, pre_ids, post_ids, full_labels, self.rope, frames, self.n_q, self.n_kv, self.hd)
         kw_args = args + (729, 27, 14, coord_rows, coord_pe)
         return _SampleLoss.apply(self, kw_args, *self._params)
+
+    # ------------------------------------------------------------------ grounding samples (llava_qwen.py:239-322)
+    def forward_ground(self, input_ids, labels, images, world_coords, boxes, box_labels, ground_token_ids=None):
+        """A ScanRefer / Multi3DRefer training sample with this module's ground_head_type: input_ids / labels / images / world_coords as
+        forward(); boxes [n, 6] the object proposals (centre xyz, size xyz; 'patch14' object features, llava_arch.py:351-376, 479-501);
+        box_labels: box_labels[0] of the reference, the indices of the target proposals.  The query is the final-norm hidden state of the
+        row whose label lies in [ground_token_ids[0], ground_token_ids[-1]] (llava_qwen.py:280-282; default: the module's).
+        Returns the grounding loss (f32 scalar with a grad_fn): infonce, or the positive-weighted BCE of 'mlp' / 'score' (:313-322)."""
+        if self.ground_head_type is None:
+            raise V3DError("forward_ground: this module models no grounding head (build it with ground_head_type)")
+        gids = self.ground_token_ids if ground_token_ids is None else [int(i) for i in ground_token_ids]
+        if not gids:
+            raise V3DError("forward_ground: no ground_token_ids")
+        tr = self.param_tree()
+        dev, dt = tr["newline"].device, tr["newline"].dtype
+        H = tr["newline"].shape[0]
+        ids = input_ids.reshape(-1).cpu()
+        lab = labels.reshape(-1).cpu()
+        at = (ids == IMAGE_TOKEN_INDEX).nonzero().flatten()
+        if at.numel() != 1:
+            raise V3DError("exactly one <image> token per sample")
+        at = int(at[0])
+        rows = ((lab >= gids[0]) & (lab <= gids[-1])).nonzero().flatten().tolist()
+        if len(rows) != 1 or rows[0] == at:
+            raise V3DError(f"forward_ground: {len(rows)} rows carry a <ground> label, the reference's predict_box takes one")
+        frames, n = images.shape[0], 14
+        n_vis = frames * n * (n + 1)
+        ground_row = rows[0] if rows[0] < at else rows[0] + n_vis - 1
+        pre_ids, post_ids = ids[:at].to(dev), ids[at + 1:].to(dev)
+        patches = ops.patchify(images.to(device=dev, dtype=dt), 14, tr["vision"]["patch_w"].shape[1])
+        coords = world_coords.to(device=dev, dtype=dt)
+        _, _, vox = ops.coord_pool_voxel(coords, 27, self.min_xyz, self.max_xyz, self.voxel_size, want_avg=False, want_vox=False)
+        bx = boxes.to(device=dev, dtype=dt).reshape(-1, 6).contiguous()
+        n_obj = bx.shape[0]
+        if n_obj < 1:
+            raise V3DError("forward_ground: no object proposals")
+        mask = ops.object_patch_mask(coords, bx).view(n_obj, -1).contiguous()
+        centres = ops.discrete_coords(bx[:, :3].contiguous(), self.min_xyz, self.max_xyz, self.voxel_size)
+        box_pe = ops.sin3d_pe(centres[None], H, dim_t=self.pe_table.dim_t)[0].contiguous()
+        labels0 = [int(i) for i in box_labels]
+        kw = {"head_type": self.ground_head_type, "temperature": self.ground_temperature}
+        if self.ground_head_type == "infonce":
+            positive = torch.zeros(n_obj + 1, dtype=torch.uint8)
+            positive[torch.tensor(labels0 or [-1], dtype=torch.int64)] = 1        # no target: the zero-target row (llava_qwen.py:304-305)
+        else:
+            positive, kw["pos_weight"] = train.ground_bce_targets(labels0, n_obj)
+        args = (patches, vox, self.pe_table, pre_ids, post_ids, ground_row, mask, box_pe, positive.to(dev), self.rope, frames,
+                self.n_q, self.n_kv, self.hd)
+        return _GroundLoss.apply(self, (args, kw), *self._params)
