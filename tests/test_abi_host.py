@@ -207,3 +207,54 @@ def test_training_entry_points_reject_bad_arguments_before_any_launch():
     assert all(rc < 0 for rc in bad), bad
     assert l.v3d_attention_backward_workspace_bytes(2, 100, 4) == (2 * 4 * 100 + 2 * 2 * 4 * 100 * 128) * 4
     assert l.v3d_colsum_workspace_bytes(65, 16) == 3 * 16 * 4
+
+
+HOST_ONLY = ("v3d_abi_version", "v3d_last_error")
+
+
+def _calls(path):
+    """Names of everything called in a Python file: `f(...)` gives f, `a.b.f(...)` gives f (ast.Call nodes only, so a name that is only
+    mentioned in a string or a docstring does not count)."""
+    import ast
+    names = set()
+    for node in ast.walk(ast.parse(open(path).read(), path)):
+        if isinstance(node, ast.Call):
+            f = node.func
+            if isinstance(f, ast.Name):
+                names.add(f.id)
+            elif isinstance(f, ast.Attribute):
+                names.add(f.attr)
+    return names
+
+
+def test_every_export_is_called_by_a_test():
+    """Every kernel the library exports is called by a GPU test (tests/test_gpu_*.py), directly through the library or through one of the
+    top-level functions / classes of v3d/ops.py whose body names it; a host-only export (the ABI version, the last error, *_host) by some
+    test.  A kernel reached only inside larger tests is checked under their bounds, not its own - this keeps the next one from landing
+    untested."""
+    import ast
+    import glob
+    ops_path = os.path.join(ROOT, "video-3d-llm_amd", "v3d", "ops.py")
+    wrappers = {}
+    for node in ast.parse(open(ops_path).read(), ops_path).body:
+        if isinstance(node, (ast.FunctionDef, ast.ClassDef)):
+            named = {n.attr for n in ast.walk(node) if isinstance(n, ast.Attribute)}
+            named |= {n.id for n in ast.walk(node) if isinstance(n, ast.Name)}
+            named |= {n.value for n in ast.walk(node) if isinstance(n, ast.Constant) and isinstance(n.value, str)}
+            for name in named:
+                if isinstance(name, str) and name.startswith("v3d_"):
+                    wrappers.setdefault(name, set()).add(node.name)
+    tests = sorted(glob.glob(os.path.join(ROOT, "tests", "test_*.py")))
+    gpu_calls, any_calls = set(), set()
+    for p in tests:
+        c = _calls(p)
+        any_calls |= c
+        if os.path.basename(p).startswith("test_gpu_"):
+            gpu_calls |= c
+    missing = []
+    for name in declared_symbols():
+        callers = {name} | wrappers.get(name, set())
+        pool = any_calls if (name in HOST_ONLY or name.endswith("_host")) else gpu_calls
+        if not callers & pool:
+            missing.append(name)
+    assert not missing, f"exports called by no test (directly or through a v3d.ops wrapper): {missing}"

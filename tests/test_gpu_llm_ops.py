@@ -754,3 +754,74 @@ def test_rope_kv_append_and_argmax(ops):
     idx = torch.zeros(1, dtype=torch.int64, device="cuda")
     ops.argmax(x.cuda(), idx)
     assert int(idx) == 1234 == int(torch.argmax(x.float()))
+
+
+def bits(t):
+    return t.cpu().view(torch.int16)
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("C", [8, 3584])
+def test_add_row_bitwise(ops, dt, C):
+    """v3d_add_row (the box-centre PE on the <coord> rows, llava_arch.py:697-700): the listed rows equal torch's (x + add) rounded once,
+    bit for bit; every other row and the columns past C of a strided x keep their bits.  Rows unsorted, the first and the last included
+    (in range only: the kernel trusts its indices)."""
+    g = torch.Generator().manual_seed(C)
+    N = 300
+    wide = (torch.randn(N, C + 16, generator=g) * 4).to(dt)
+    add = torch.randn(C, generator=g).to(dt)
+    rows = torch.tensor([17, 0, N - 1, 5, 123, 6, 299 - 77], dtype=torch.int64)
+    xd = wide.cuda()
+    ops.add_row(xd[:, :C], rows.cuda(), add.cuda())
+    want = wide.clone()
+    want[rows, :C] = (wide[rows, :C].float() + add.float()).to(dt)
+    assert torch.equal(bits(xd), want.view(torch.int16))
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("rows,cols,n_copies,cap,width", [(37, 8, 1, 40, 8), (700, 512, 3, 768, 520), (6720, 256, 32, 6800, 264),
+                                                          (2100, 8192, 3, 2112, 8200)])
+def test_copy_rows_bcast_bitwise(ops, dt, rows, cols, n_copies, cap, width):
+    """v3d_copy_rows_bcast into the engine's [G, cap, width] caches (cap > rows): every copy equals the source rows bit for bit, every cell
+    past rows x cols of a copy keeps its sentinel.  The source is a column window of a wider tensor; 2100 x 8192 is more than
+    8192 blocks x 256 threads of 8-element vectors, so the grid strides."""
+    g = torch.Generator().manual_seed(rows + n_copies)
+    src_wide = torch.randn(rows, cols + 24, generator=g).to(dt).cuda()
+    src = src_wide[:, 8:8 + cols]
+    dst = torch.empty(n_copies, cap, width, dtype=dt, device="cuda")
+    dst.view(torch.int16).fill_(0x7A5A)
+    ops.copy_rows_bcast(src, dst, cols)
+    got = bits(dst)
+    want = bits(src)
+    for c in range(n_copies):
+        assert torch.equal(got[c, :rows, :cols], want), f"copy {c}"
+    rest = got.clone()
+    rest[:, :rows, :cols] = 0x7A5A
+    assert bool((rest == 0x7A5A).all()), "a cell outside rows x cols was written"
+
+
+@pytest.mark.parametrize("M", [1, 63, 64, 65, 200])
+@pytest.mark.parametrize("n_eos", [0, 1, 3])
+def test_eos_update_vs_set_membership(ops, M, n_eos):
+    """v3d_eos_update against a Python set-membership loop over several steps: done rows stay done whatever comes next, n_done == done.sum()
+    after every call, an EOS id above 2^31, more rows than the 64 lanes of its one wave."""
+    g = torch.Generator().manual_seed(M * 3 + n_eos)
+    eos = [151645, (1 << 33) + 7, 151643][:n_eos]
+    eos_d = torch.tensor(eos, dtype=torch.int64).cuda()
+    done_d = torch.zeros(M, dtype=torch.int32, device="cuda")
+    n_done = torch.zeros(1, dtype=torch.int32, device="cuda")
+    done = [0] * M
+    for step in range(4):
+        tok = torch.randint(0, 152000, (M,), generator=g)
+        pick = torch.rand(M, generator=g)
+        for m in range(M):
+            if eos and pick[m] < 0.15:
+                tok[m] = eos[int(pick[m] * 100) % len(eos)]
+        if step == 3:
+            tok[:] = 11                                                   # no EOS at all: every done row must stay done
+        if step == 1:
+            tok[0] = 7                                                    # the large EOS id's low 32 bits: not an EOS
+        ops.eos_update(tok.cuda(), eos_d, done_d, n_done)
+        done = [1 if (d or int(t) in set(eos)) else 0 for d, t in zip(done, tok.tolist())]
+        assert done_d.cpu().tolist() == done, f"step {step}"
+        assert int(n_done.item()) == sum(done)

@@ -383,3 +383,173 @@ def test_resize_rejects_bad_windows(ops):
         ops.resize_crop_rgb(fr, (38, 51), crop=(0, 40, 38, 24))          # window leaves the resized image
     with pytest.raises(ops.V3DError):
         ops.resize_crop_rgb(torch.zeros((1, 4800, 64, 3), dtype=torch.uint8).cuda(), (38, 51))      # 126x vertical reduction: more than 32 taps
+
+
+# ------------------------------------------------------------------------------ bounds, resize, clamp (video_utils.py:232-236, 268-296)
+
+
+def oracle_bounds(world):
+    """The reference's `boundry` (video_utils.py:268-273): min / max of each axis over every coordinate, NaN if any is NaN."""
+    flat = torch.from_numpy(np.ascontiguousarray(world)).reshape(-1, 3)
+    return np.array([f(flat[:, a]).item() for a in range(3) for f in (torch.min, torch.max)], np.float32)
+
+
+@pytest.mark.parametrize("shape", [(32, 480, 640), (2, 3, 5), (3, 7, 1)])
+def test_unproject_bounds_vs_oracle(ops, shape):
+    """v3d_unproject_bounds_u16 (two-stage min / max of the full-resolution back-projection) against the oracle's unproject + min / max,
+    and bit for bit against amin / amax of ops.unproject on the same frames (same arithmetic, geometry.hip is built without
+    contraction).  ScanNet's 32 x 480 x 640 with zero-depth pixels and a few at 65535; and frames so small that most of the 64 blocks
+    per frame see no pixel, whose +-inf partials must not reach the result."""
+    V, H, W = shape
+    depth, K, P = synth_scene(V, H=H, W=W, seed=H + W)
+    depth[:, -1, -1] = 65535
+    depth[0, 0, 0] = 65535
+    d16 = torch.from_numpy(depth.view(np.int16)).cuda()
+    got = ops.unproject_bounds(d16, dev(K), dev(P)).cpu().numpy()
+    np.testing.assert_allclose(got, oracle_bounds(O.unproject(K, P, depth.astype(np.float32))), rtol=1e-6, atol=1e-6)
+    full = ops.unproject(dev(K), dev(P), dev(depth.astype(np.float32))).reshape(-1, 3)
+    same = torch.stack([full.amin(0), full.amax(0)], 1).reshape(6).cpu().numpy()
+    assert np.array_equal(got.view(np.int32), same.view(np.int32)), (got, same)
+    again = ops.unproject_bounds(d16, dev(K), dev(P)).cpu().numpy()
+    assert np.array_equal(got.view(np.int32), again.view(np.int32))
+
+
+def nearest_index(n_src, size):
+    """The nearest-neighbour rule of cv2.resize(INTER_NEAREST) restated: src = min(floor(dst * n_src / size), n_src - 1)."""
+    return np.minimum(np.floor(np.arange(size) * (n_src / size)).astype(int), n_src - 1)
+
+
+@pytest.mark.parametrize("kind", ["f32", "f16", "bf16"])
+@pytest.mark.parametrize("size", [384, 100, 520])
+def test_unproject_resized_vs_oracle(ops, kind, size):
+    """VideoProcessor.preprocess(strategy="resize"): the oracle's full-resolution unproject gathered through the nearest index map on both
+    axes, then cast.  384: the eight-pixel kernel; 100: the scalar one (size % 8 != 0); 520: upsampling (size > H), eight-pixel."""
+    depth, K, P = synth_scene(3, seed=size)
+    d16 = torch.from_numpy(depth.view(np.int16)).cuda()
+    got = host32(ops.unproject_resized(d16, dev(K), dev(P), size, KINDS[kind]))
+    full = O.unproject(K, P, depth.astype(np.float32))
+    want = O.round_to(full[:, nearest_index(480, size)][:, :, nearest_index(640, size)], kind)
+    assert got.shape == (3, size, size, 3)
+    if kind == "f32":
+        np.testing.assert_allclose(got, want, rtol=1e-6, atol=1e-6)
+    else:                                   # an f32 value 1e-6 off can round to the neighbouring 16-bit value, as in the sampled test
+        d = ulp16(got, want, kind)
+        assert d.max() <= 1 and (d != 0).mean() < 1e-3
+
+
+def clamp_ref(x, lo, hi):
+    """calculate_world_coords(do_normalize=True) (video_utils.py:232-234): f32 torch.maximum, then torch.minimum - NaN stays NaN."""
+    return torch.minimum(torch.maximum(x.float(), torch.tensor(lo, dtype=torch.float32)), torch.tensor(hi, dtype=torch.float32))
+
+
+def same_bits(a, b):
+    a, b = a.cpu(), b.cpu()
+    if a.dtype == torch.float32:
+        return torch.equal(a.view(torch.int32), b.view(torch.int32))
+    return torch.equal(a.view(torch.int16), b.view(torch.int16))
+
+
+@pytest.mark.parametrize("kind", ["f32", "f16", "bf16"])
+@pytest.mark.parametrize("n_points", [1000, 32 * 384 * 384])
+def test_clamp_xyz_equals_torch(ops, kind, n_points):
+    """v3d_clamp_xyz bit for bit against the reference's clamp: values on a bound, outside it, +-inf and NaN (kept, as torch keeps it);
+    a point count that is not a multiple of 256, and 32 x 384 x 384 points, more than the 8192-block grid covers in one pass."""
+    dt = KINDS[kind]
+    g = torch.Generator().manual_seed(n_points)
+    lo, hi = [-3.25, -2.5, 0.125], [4.0, 2.75, 2.5]
+    x = (torch.rand(n_points, 3, generator=g) - 0.5) * torch.tensor([12.0, 10.0, 6.0])
+    x[:3] = torch.tensor(lo)
+    x[3:6] = torch.tensor(hi)
+    x[6] = float("inf")
+    x[7] = -float("inf")
+    x[8] = float("nan")
+    x[9, 1] = float("nan")
+    x[-1] = torch.tensor([float("nan"), float("inf"), -float("inf")])
+    x[torch.rand(n_points, 3, generator=g) < 1e-3] = float("nan")
+    x = x.to(dt)
+    got = ops.clamp_xyz(x.cuda(), lo, hi)
+    want = clamp_ref(x, lo, hi).to(dt)
+    nan = torch.isnan(want)
+    assert torch.equal(torch.isnan(got.cpu()), nan), "a NaN was replaced (or one was made)"
+    assert same_bits(torch.where(nan, 0, got.cpu()), torch.where(nan, 0, want))
+    if kind != "f32":
+        # the product path clamps coordinates already rounded to the 16-bit dtype (pipeline.py: unproject_sampled in dt, then
+        # clamp_xyz); the reference clamps in f32 and the driver rounds afterwards - the two orders must agree bit for bit
+        x32 = x.float() + (torch.rand(n_points, 3, generator=g) - 0.5) * 1e-2
+        rounded_first = ops.clamp_xyz(x32.to(dt).cuda(), lo, hi).cpu()
+        ref_order = clamp_ref(x32, lo, hi).to(dt)
+        nan = torch.isnan(ref_order)
+        assert torch.equal(torch.isnan(rounded_first), nan)
+        assert same_bits(torch.where(nan, 0, rounded_first), torch.where(nan, 0, ref_order))
+
+
+def nonfinite_scene():
+    """Three 480 x 640 frames: frame 0 finite; frame 1 with -inf in two pose entries (x = -inf * x_cam: NaN where x_cam = 0, +-inf
+    elsewhere; y = -inf); frame 2 with the all -inf pose ScanNet writes when camera tracking failed (every coordinate NaN)."""
+    depth, K, P = synth_scene(3, seed=21)
+    P[1, 0, 0] = -np.inf
+    P[1, 1, 3] = -np.inf
+    P[2] = -np.inf
+    return depth, K, P
+
+
+def nonfinite_same(got, want, rtol=1e-6, atol=1e-6):
+    """NaN, +inf and -inf at the same positions; the finite values close."""
+    for f in (np.isnan, np.isposinf, np.isneginf):
+        assert np.array_equal(f(got), f(want)), f.__name__
+    fin = np.isfinite(want)
+    np.testing.assert_allclose(got[fin], want[fin], rtol=rtol, atol=atol)
+
+
+def test_nonfinite_pose_follows_torch(ops):
+    """A pose with -inf entries: the back-projections put NaN / +-inf where the oracle does, clamp_xyz keeps every NaN and clamps +-inf
+    to the box, and unproject_bounds returns NaN on the axes whose min / max is NaN in the reference (torch's min / max propagate it)."""
+    depth, K, P = nonfinite_scene()
+    want = O.unproject(K, P, depth.astype(np.float32))
+    assert np.isnan(want[1]).any() and np.isposinf(want[1]).any() and np.isneginf(want[1]).any() and np.isnan(want[2]).all()
+    d16 = torch.from_numpy(depth.view(np.int16)).cuda()
+    got = ops.unproject(dev(K), dev(P), dev(depth.astype(np.float32)))
+    nonfinite_same(host32(got), want)
+    nonfinite_same(host32(ops.unproject_sampled(d16, dev(K), dev(P), 384)), O.resize_crop_coords(want, 384))
+    nonfinite_same(host32(ops.unproject_resized(d16, dev(K), dev(P), 100)), want[:, nearest_index(480, 100)][:, :, nearest_index(640, 100)])
+    lo, hi = [-3.0, -2.0, -1.0], [3.0, 2.0, 4.0]
+    clamped = ops.clamp_xyz(got.clone(), lo, hi).cpu()
+    ref = clamp_ref(torch.from_numpy(want), lo, hi)
+    nonfinite_same(clamped.numpy(), ref.numpy())
+    assert torch.equal(torch.isnan(clamped), torch.isnan(got.cpu()))
+    # frames 0 + 1: x NaN, y_min -inf; all three frames: every axis NaN
+    for v in (2, 3):
+        b = ops.unproject_bounds(d16[:v].contiguous(), dev(K[:v]), dev(P[:v])).cpu().numpy()
+        nonfinite_same(b, oracle_bounds(want[:v]))
+    assert np.isnan(b).all()
+
+
+def test_norm_strategy_boundry_with_a_nonfinite_pose(ops, tmp_path):
+    """VideoProcessor.preprocess under a "norm" strategy on scene files whose second pose has -inf entries: `boundry` is the reference's
+    expression (video_utils.py:232-236, 268-273: clamp with torch.maximum / minimum, then min / max per axis).  axis_align @ pose already
+    spreads the -inf into NaN (0 * -inf), so every coordinate of that frame is NaN and so is every bound - finite before the fix."""
+    import types
+    import llava.video_utils as vu
+    from scene_files import write_frames
+    depth, K, P = synth_scene(2, H=48, W=64, seed=4)
+    K[:, 0, 2], K[:, 1, 2] = 31.5, 23.5
+    poses = P.astype(np.float64)
+    poses[1, 0, 0] = -np.inf
+    poses[1, 1, 3] = -np.inf
+    align = np.eye(4)
+    align[:3, 3] = [0.25, -0.5, 0.0]
+    files = write_frames(str(tmp_path / "posed_images" / "scene0000_00"), depth, poses, rgb=np.zeros((2, 48, 64, 3), np.uint8), ext=".jpg")
+    vp = object.__new__(vu.VideoProcessor)
+    vp.video_folder = str(tmp_path)
+    vp.frame_sampling_strategy = "uniform-norm"
+    vid = "scannet/scene0000_00"
+    vp.scene = {vid: {"axis_align_matrix": align.tolist(), "depth_cam2img": K[0].astype(np.float64).tolist(),
+                      "images": [{"img_path": "posed_images/scene0000_00/" + f.split("/")[-1]} for f in files]}}
+    vp.scan2obj = {vid: [[0.0, 0.1, 0.2, 1.0, 1.0, 1.0]]}
+    lo, hi = torch.tensor([-1.5, -1.0, 0.2]), torch.tensor([1.5, 0.75, 3.0])
+    vp.pc_min, vp.pc_max = {"scene0000_00": lo}, {"scene0000_00": hi}
+    out = vp.preprocess(vid, types.SimpleNamespace(crop_size={"height": 24, "width": 24}), force_sample=True, frames_upbound=2)
+    world = O.unproject(np.repeat(K[:1], 2, 0), np.stack([align @ p for p in poses]).astype(np.float32), depth.astype(np.float32))
+    want = oracle_bounds(clamp_ref(torch.from_numpy(world), lo.tolist(), hi.tolist()).numpy())
+    assert np.isnan(want).all()
+    nonfinite_same(out["boundry"].numpy(), want, rtol=2e-6, atol=2e-6)

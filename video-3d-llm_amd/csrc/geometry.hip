@@ -147,7 +147,12 @@ __global__ __launch_bounds__(256) void unproject_sampled_kernel(const uint16_t* 
 // Bounds of the FULL-resolution back-projection (llava/video_utils.py:268-273: min / max of world_coords over all V*H*W
 // pixels, taken before the resize and crop) without materialising the 118 MB tensor: every pixel is back-projected with the
 // same arithmetic as unproject_f32_kernel and only the running min / max survive.  Stage 1: one partial (6 floats) per block;
-// stage 2: one block folds the partials.  min / max are exact, so the two-stage order does not matter.
+// stage 2: one block folds the partials.  min / max are exact, so the two-stage order does not matter.  torch's min() / max()
+// return NaN when any element is NaN (a non-finite pose gives NaN coordinates), fminf / fmaxf would drop it: both stages
+// reduce with nan_min / nan_max, which carry a NaN from either side.
+__device__ __forceinline__ float nan_min(float a, float b) { return (a < b || a != a) ? a : b; }
+__device__ __forceinline__ float nan_max(float a, float b) { return (a > b || a != a) ? a : b; }
+
 __global__ __launch_bounds__(256) void unproject_bounds_kernel(const uint16_t* __restrict__ depth, const float* __restrict__ K,
                                                                const float* __restrict__ P, int H, int W, float* __restrict__ partial) {
   const int v = blockIdx.y;
@@ -159,15 +164,15 @@ __global__ __launch_bounds__(256) void unproject_bounds_kernel(const uint16_t* _
     float o[3];
     backproject(c, (float)col, (float)row, (float)(int)depth[(size_t)v * n + pix], o);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], o[a]); hi[a] = fmaxf(hi[a], o[a]); }
+    for (int a = 0; a < 3; ++a) { lo[a] = nan_min(lo[a], o[a]); hi[a] = nan_max(hi[a], o[a]); }
   }
   __shared__ float sm[4][6];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
-      lo[a] = fminf(lo[a], __shfl_xor(lo[a], off));
-      hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off));
+      lo[a] = nan_min(lo[a], __shfl_xor(lo[a], off));
+      hi[a] = nan_max(hi[a], __shfl_xor(hi[a], off));
     }
   }
   const int wave = threadIdx.x >> 6;
@@ -179,7 +184,7 @@ __global__ __launch_bounds__(256) void unproject_bounds_kernel(const uint16_t* _
   if (threadIdx.x < 6) {
     const int a = threadIdx.x;
     float r = sm[0][a];
-    for (int w = 1; w < 4; ++w) r = (a & 1) ? fmaxf(r, sm[w][a]) : fminf(r, sm[w][a]);
+    for (int w = 1; w < 4; ++w) r = (a & 1) ? nan_max(r, sm[w][a]) : nan_min(r, sm[w][a]);
     partial[((size_t)v * gridDim.x + blockIdx.x) * 6 + a] = r;
   }
 }
@@ -189,14 +194,14 @@ __global__ __launch_bounds__(256) void bounds_fold_kernel(const float* __restric
   float r[6] = {INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY};
   for (int i = threadIdx.x; i < n_partials; i += 256)
 #pragma unroll
-    for (int a = 0; a < 6; ++a) r[a] = (a & 1) ? fmaxf(r[a], partial[(size_t)i * 6 + a]) : fminf(r[a], partial[(size_t)i * 6 + a]);
+    for (int a = 0; a < 6; ++a) r[a] = (a & 1) ? nan_max(r[a], partial[(size_t)i * 6 + a]) : nan_min(r[a], partial[(size_t)i * 6 + a]);
 #pragma unroll
   for (int a = 0; a < 6; ++a) sm[threadIdx.x][a] = r[a];
   __syncthreads();
   if (threadIdx.x < 6) {
     const int a = threadIdx.x;
     float x = sm[0][a];
-    for (int i = 1; i < 256; ++i) x = (a & 1) ? fmaxf(x, sm[i][a]) : fminf(x, sm[i][a]);
+    for (int i = 1; i < 256; ++i) x = (a & 1) ? nan_max(x, sm[i][a]) : nan_min(x, sm[i][a]);
     bounds[a] = x;
   }
 }
@@ -415,7 +420,7 @@ __global__ __launch_bounds__(256) void clamp_xyz_kernel(T* __restrict__ xyz, int
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_points * 3; i += (int64_t)gridDim.x * 256) {
     const int a = (int)(i % 3);
     const float v = to_f32(xyz[i]);
-    xyz[i] = from_f32<T>(fminf(fmaxf(v, lo[a]), hi[a]));
+    if (v == v) xyz[i] = from_f32<T>(fminf(fmaxf(v, lo[a]), hi[a]));     // torch.maximum / minimum keep a NaN (as voxelise)
   }
 }
 
