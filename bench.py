@@ -9,13 +9,18 @@ One step = one (scene, question) through the whole hot path with inputs resident
 Random-init weights at the true widths, synthetic inputs, bf16, a DIFFERENT synthetic scene per step (all resident
 in HBM before the timed region).  Every scene runs the complete path; scenes are prefilled one by one and decoded in groups
 (--decode-group, default 16) that share each pass over the weights.
-The default N = 1 line also carries `roofline` (the dominant kernel: the Qwen2 gate/up GEMM, MFMA), `roofline_north_star` (3D-PE +
-fusion kernel, HBM), `roofline_attention`, `fp8_config3` (the same step with e4m3 LLM weights, BASELINE configs[3]),
-`train_config4` (one training sample end to end on one GPU: tower + projector + Qwen2 with labels, backward, AdamW; v3d/train.py),
-`cached_questions` (scene-level reuse, SURVEY 8 f1: further questions about an already prefilled scene), `ground_config2`
-(the ScanRefer / Multi3DRefer grounding forward at 32 frames / 50 proposals, BASELINE configs[2], one GPU) and `cpu_baseline`.
+The line also carries `roofline` (the dominant kernel: the Qwen2 gate/up GEMM, MFMA), `roofline_north_star` (3D-PE + fusion kernel,
+HBM) and `roofline_attention`, from HIP events stamped around those kernels inside the timed steps.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+A plain run does only what the headline needs: set up, warm up, time the K steps, dump the outputs if asked, print the line.
+--full (N = 1) then adds the measurements that take runs of their own: `s4096_proxy` (BASELINE.json's 4096-token proxy),
+`cached_questions` (scene-level reuse, SURVEY 8 f1: further questions about an already prefilled scene), `decode_step` (against its
+HBM roofline), `eval_runner` / `reuse_runner` (the eval loop from files on disk), `ground_config2` (the ScanRefer / Multi3DRefer
+grounding forward at 32 frames / 50 proposals, BASELINE configs[2], one GPU), `fp8_config3` (the same step with e4m3 LLM weights,
+BASELINE configs[3]), `train_config4` (one training sample end to end on one GPU: tower + projector + Qwen2 with labels, backward,
+AdamW; v3d/train.py) and `cpu_baseline`; the --no-* options leave parts of that out.
+
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (RANK / WORLD_SIZE in the
 environment), or started plainly - then THIS process, before it touches the GPU, starts exactly that command as a child (one rank
@@ -573,25 +578,55 @@ def dry_run(a, rank, world):
         dist.destroy_process_group()
 
 
-def main():
+def extra_plan(a, world):
+    """The measurements a run makes beside the headline: none without --full, and none with more than one rank (the extras are
+    one-GPU figures); with --full, what the --no-* options leave in."""
+    if not a.full or world != 1:
+        return set()
+    if a.eval_runner_only:
+        plan = {"eval_runner"}
+    elif a.no_extras:
+        plan = set()
+    else:
+        plan = {"s4096_proxy", "cached_questions", "decode_step", "eval_runner", "ground_config2"}
+        if not a.fp8 and not a.no_fp8_extra:
+            plan.add("fp8_config3")
+        if not a.no_train_extra:
+            plan.add("train_config4")
+    if not a.no_cpu_baseline:
+        plan.add("cpu_baseline")
+    return plan
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=16)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: after the headline, also run every other measurement (proxy size, scene reuse, decode roofline, eval loop from "
+                         "files, grounding, fp8, training step, CPU baseline) and add it to the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-overlap", action="store_true", help="one scene at a time: no decode groups, no prefill/decode overlap")
     ap.add_argument("--decode-group", type=int, default=16, help="scenes decoded together per pass over the weights (1..32)")
     ap.add_argument("--answer-batch", type=int, default=32, help="cached_questions / reuse_runner: questions answered together (1..32)")
     ap.add_argument("--fp8", action="store_true", help="BASELINE configs[3]: e4m3 linears in the Qwen2 prefill; the headline line becomes that run")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra measurements appended to the default N=1 line (fp8, cached questions, grounding)")
-    ap.add_argument("--no-fp8-extra", action="store_true", help="skip only the configs[3] extra")
-    ap.add_argument("--no-train-extra", action="store_true", help="skip only the configs[4] (language-model training step) extra")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip every measurement but the CPU baseline")
+    ap.add_argument("--no-fp8-extra", action="store_true", help="with --full: skip only the configs[3] extra")
+    ap.add_argument("--no-train-extra", action="store_true", help="with --full: skip only the configs[4] (language-model training step) extra")
     ap.add_argument("--prefill-streams", type=int, default=2, help="streams that prefill consecutive scenes side by side (each with its own scratch)")
-    ap.add_argument("--eval-runner-only", action="store_true", help="after the headline run only the eval_runner extra (development)")
+    ap.add_argument("--eval-runner-only", action="store_true", help="with --full: after the headline run only the eval_runner extra (development)")
     ap.add_argument("--scenes", type=int, default=8, help="distinct synthetic scenes resident in HBM, cycled over the steps")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the headline run's answer token ids to DIR/answer_token_ids.npy (float64)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    if a.eval_runner_only and not a.full:
+        ap.error("--eval-runner-only selects among the --full measurements: add --full")
+    return a
+
+
+def main():
+    a = parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         raise SystemExit(launch_ranks(a.gpus, sys.argv[1:]))          # (nothing above has touched the GPU: `import torch` does not)
@@ -608,8 +643,9 @@ def main():
     if rehearsal:
         local = 0
         os.environ["V3D_GEMM_STREAMK"] = "0"      # ranks share one card: the GEMM's split-K tail assumes one tail launch on the chip
+    plan = extra_plan(a, world)
     loader_pool, n_workers = None, 0
-    if world == 1 and (a.eval_runner_only or not a.no_extras):     # the eval_runner extra's decoding processes: forked before the GPU is touched
+    if "eval_runner" in plan:     # the eval_runner extra's decoding processes: forked before the GPU is touched
         from v3d import eval_scanqa as _E, frame_io
         n_workers = _E.default_workers()
         loader_pool = frame_io.make_pool(n_workers)
@@ -681,7 +717,7 @@ def main():
     if rank == 0 and a.dump_outputs:
         dump_outputs(a.dump_outputs, rows)
     extras = {}
-    if world == 1 and not a.no_extras and not a.eval_runner_only:
+    if "s4096_proxy" in plan:
         # BASELINE.json's stated synthetic proxy (a 4096-token sequence; SURVEY 8(d) asks for it NEXT to the true shape).  No frame count
         # of the real path gives 4096 visual rows (a frame is 14 x 15 = 210 rows), so the proxy is 19 frames x 210 = 3990
         # visual rows + 14 + 92 text ids = exactly 4096; everything else as in the headline.
@@ -699,9 +735,9 @@ def main():
             "value": a.steps / t4, "unit": "scenes/s", "ms_per_step": t4 / a.steps * 1e3, "frames": PF, "seq_len": 4096,
             "attention_us_per_layer": a_us, "attention_frac_of_2.5PF": 2.0 * 4096 * 4096 * 128 * 28 / a_us / 1e6 / 2500.0,
             "gate_up_gemm_us": st4["gemm"].mean_us(), "gate_up_gemm_frac_of_2.5PF": 2.0 * 4096 * 37888 * 3584 / st4["gemm"].mean_us() / 1e6 / 2500.0}
-    if world == 1 and a.eval_runner_only:
+    if a.eval_runner_only and "eval_runner" in plan:
         extras["eval_runner"], extras["reuse_runner"] = measure_eval_runner(eng, dev, max(48, 3 * a.steps), loader_pool, n_workers)
-    elif world == 1 and not a.no_extras:
+    elif "cached_questions" in plan:
         AB = max(1, min(32, a.answer_batch))
         nq, scene_ms = measure_cached_questions(eng, ops, scenes[0], dev, n_groups=max(1, a.steps // 4), group=AB)
         extras["cached_questions"] = {
@@ -722,7 +758,7 @@ def main():
             "what": "BASELINE configs[2] on one GPU: ScanRefer / Multi3DRefer grounding forward, 32 frames, 50 object proposals, "
                     "infonce head (prefill only, no decode)",
             "value": measure_grounding(eng, ops, scenes, dev, max(4, a.steps // 2)), "unit": "scenes/s"}
-        if not a.fp8 and not a.no_fp8_extra:
+        if "fp8_config3" in plan:
             del eng
             torch.cuda.empty_cache()
             eng8 = Engine(cfg, sd, dtype=dtype, device=dev, max_frames=FRAMES, llm_fp8=True)
@@ -736,7 +772,7 @@ def main():
                 "gate_up_gemm_us": g8, "gate_up_gemm_tflops": 2.0 * (TEXT_PRE + FRAMES * 210 + TEXT_POST) * 37888 * 3584 / g8 / 1e6,
                 "mfma_peak_tflops": 5000.0}
             del eng8
-        if not a.no_train_extra:
+        if "train_config4" in plan:
             eng = None
             torch.cuda.empty_cache()
             try:
@@ -808,7 +844,7 @@ def main():
                                    "mfma_busy_frac_pmc": attn_busy},
         }
         line.update(extras)
-        if world == 1 and not a.no_cpu_baseline:
+        if "cpu_baseline" in plan:
             # n = ALL host cores this process may run on (printed in the line as `cores`): the scheduler affinity, cut to
             # the container's CPU quota where one is set (256 threads on a 16-core quota ran the same sample 2.6x SLOWER than 16)
             cores, why = usable_cores()
