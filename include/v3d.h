@@ -185,6 +185,24 @@ int v3d_gemm_fp8(const void* A, int64_t lda, const float* scale_a, const void* W
 int v3d_rmsnorm_quantize_fp8(const void* x, int64_t ldx, const void* weight, float eps, int64_t rows, int cols, int dtype,
                              void* q, int64_t ldq, float* scale, void* stream);
 
+/* MXFP4 (OCP MX v1.0) weights for the LLM linears; not part of the reference (contract and tolerances are stated in
+ * tests/test_gpu_fp4.py, the format is restated on the host in tests/mxfp4_check.py).  A weight matrix W [N, K]
+ * (K % 128 == 0) is the pair
+ *   q [N, K/2] bytes: two e2m1 codes per byte, the even k in the low nibble; code = sign(1) | exp(2) | mant(1), magnitudes
+ *                     {0, 0.5, 1, 1.5, 2, 3, 4, 6};
+ *   e [N, K/32] bytes: one E8M0 exponent per 32 consecutive k of a row, value 2^(e - 127); 0xFF is never written.
+ * v3d_quantize_mxfp4_rows: w [rows, cols] (f16/bf16, finite) -> (q, e), row strides ldq / lde in bytes.  Per block:
+ *   e = clamp(floor(log2(amax)) - 2 + 127, 0, 254), an all-zero block gets e = 127; codes = w * 2^(127 - e) rounded to the
+ *   nearest e2m1 value, ties to the even code, saturating at +-6; a zero magnitude carries no sign.
+ * v3d_gemm_mxfp4 (prefill, W4A8): y[m,n] = scale_a[m] * sum_k A[m,k] * deq(W)[n,k], A [M,K] e4m3 (lda bytes) + scale_a as
+ *   v3d_quantize_fp8_rows / v3d_rmsnorm_quantize_fp8 write them; f32 accumulation; N % 256 == 0, K % 128 == 0, any M >= 1;
+ *   epilogues NONE / BIAS / RES / SWIGLU with the codes, rounding order and row interleave of v3d_gemm_fp8. */
+int v3d_quantize_mxfp4_rows(const void* w, int64_t ldw, int64_t rows, int cols, int dtype, void* q, int64_t ldq, void* e,
+                            int64_t lde, void* stream);
+int v3d_gemm_mxfp4(const void* A, int64_t lda, const float* scale_a, const void* Wq, int64_t ldw, const void* We, int64_t lde,
+                   const void* bias, const void* res, int64_t ldr, void* out, int64_t ldo, int M, int N, int K, int out_dtype,
+                   int epilogue, void* stream);
+
 /* ------------------------------------------------------------------ norms / rotary ------ */
 
 /* K13  Qwen2RMSNorm, modeling_qwen2.py:85-90: out = weight * T(x * rsqrt(mean(x^2) + eps)), f32 inside. */
@@ -309,6 +327,16 @@ int v3d_linear_decode_rows_fuses_norm(int M, int N, int K, int epilogue);
 int v3d_linear_decode_fp8_rows(const void* x, int64_t ldx, int M, const void* W8, int64_t ldw, const float* scale_w,
                                const void* bias, const void* res, int64_t ldr, void* out, int64_t ldo, int N, int K,
                                int dtype, int epilogue, void* stream);
+
+/* The decode linear over MXFP4 weights (W4A16): Wq [N, K/2] codes (row stride ldw bytes) and We [N, K/32] exponents (row
+ * stride lde bytes) as v3d_quantize_mxfp4_rows writes them; y[m,n] = sum_k deq(W)[n,k] x[m,k] with deq(W) widened exactly to
+ * the activation type, f32 accumulation, then the epilogue of v3d_linear_decode.  K % 128 == 0.  M = 1: VALU form;
+ * M = 2..32 with K % 256 == 0, N % 16 == 0 (SWIGLU: N % 128 == 0), lde % 8 == 0 and We 8-byte aligned: matrix-core form (a
+ * row's result depends neither on the other rows nor on M); other shapes: VALU form, M <= 4.  Not a reference code path
+ * (tolerance: tests/test_gpu_fp4.py). */
+int v3d_linear_decode_mxfp4_rows(const void* x, int64_t ldx, int M, const void* Wq, int64_t ldw, const void* We, int64_t lde,
+                                 const void* bias, const void* res, int64_t ldr, void* out, int64_t ldo, int N, int K,
+                                 int dtype, int epilogue, void* stream);
 
 /* Decode-step K14 + cache append in one launch: rotary at position `pos` on the n_q + n_kv heads at the start
  * of the QKV row (in place), rotated k and v copied to cache_row = [k heads | v heads]. */

@@ -1,0 +1,708 @@
+// MXFP4 (OCP MX v1.0: e2m1 codes + one E8M0 exponent per 32 k) weights for the LLM linears.  Not a reference code path (the
+// reference runs 16-bit only); the contract is include/v3d.h and tests/test_gpu_fp4.py.
+//   W [N, K]  ->  q [N, K/2] bytes (even k in the low nibble)  +  e [N, K/32] bytes (2^(e-127))
+//   prefill (W4A8):  y[m,n] = sa[m] * sum_k qa[m,k] * deq(W)[n,k]      qa/sa as v3d_quantize_fp8_rows writes them
+//   decode  (W4A16): y[m,n] = sum_k x[m,k] * deq(W)[n,k]               deq(W) widened exactly to the activation type
+//
+// v_mfma_scale_f32_16x16x128_f8f6f4 with an fp4 first operand (cbsz = 4) and an e4m3 second operand, measured with
+// tools/probes/mfma_scale_f4_layout.hip:
+//   * fp4 operand: lane l holds row l&15 and the 32 k [32 g, +32), g = l>>4, as 16 bytes in registers 0..3 (registers 4..7 are
+//     ignored); nibble i of those 16 bytes (low nibble of a byte first) is k = 32 g + i;
+//   * e4m3 operand against it: lane l holds row l&15; bytes 0..15 (registers 0..3) are k = 16 g + 0..15 and bytes 16..31
+//     (registers 4..7) are k = 64 + 16 g + 0..15.  (Two e4m3 operands, gemm_fp8.hip, only need the SAME order on both sides,
+//     which is why that probe could call it "k-bytes [32 g, +32)"; against an fp4 operand the true order shows.)  The activation
+//     fragment is therefore the 16-byte chunks g and 4 + g of the lane's 128-byte row;
+//   * the block-scale register is per lane: byte `opsel` of lane l's register scales the 32 k that lane l holds, i.e. exactly
+//     one MX block of row l&15.  The public [N, K/32] scale array therefore needs no repack: lane l loads byte
+//     e[n0 + l&15][4*kt + (l>>4)] and passes it with opsel 0 (the activation side passes the constant 127 = 2^0);
+//   * C/D as every 16x16 MFMA (lane l: column l&15, rows 4*(l>>4) + r).
+// v_cvt_scalef32_pk_{bf16,f16,f32}_fp4(src, scale, sel) widens byte `sel` of src: element 0 is the low nibble, element 1 the
+// high nibble, multiplied by 2^(exponent field of scale - 127) (the mantissa of the scale is ignored).
+//
+// Prefill kernel = gemm_fp8_kernel's structure: 256 x 256 tile, K-step 128, 8 waves of 128 x 64, DMA staging, four phases of
+// 8 MFMAs, one barrier per K-step.  The activation tile keeps its 128-byte rows and XOR swizzle; the weight tile has 64-byte
+// rows (4 chunks of 16 bytes, chunk ^ ((row >> 2) & 3): the 16 rows that read one chunk together spread over all banks), so a
+// stage is 48 KiB instead of 64 and a weight fragment is ONE ds_read_b128.  The 32 KiB that frees stays unused (the epilogue
+// needs 64 KiB, two stages give 96).  Measured once (profiles/fp4_linears.txt) this kernel takes 1.06-1.12 x gemm_fp8_kernel's time;
+// only those end-to-end times were measured, no counters.  HYPOTHESIS, not measured: the four block exponents a lane fetches per
+// K-step are single-byte global loads at a row stride of lde (uncoalesced, issued beside the MFMA phases) and cost more than the
+// halved weight staging saves.  FOLLOW-UP (open, not a closed design): stage the K-step's [256 x 4] exponent tile (1 KiB) through
+// LDS with the weight DMA, or repack the exponents at load so that a lane's four bytes are one dword; the freed LDS also allows
+// a third stage.
+#include "v3d_common.h"
+
+namespace v3d {
+
+using f4_v8i = __attribute__((ext_vector_type(8))) int;
+using f4_v4i = __attribute__((ext_vector_type(4))) int;
+using f4_f32x4 = __attribute__((ext_vector_type(4))) float;
+using f4_f32x2 = __attribute__((ext_vector_type(2))) float;
+
+constexpr int F4_BK = 128;                               // k elements per K-step
+constexpr int F4_ATILE = 256 * F4_BK;                    // e4m3 activations: 32 KiB
+constexpr int F4_WROW = F4_BK / 2;                       // 64 bytes of codes per weight row per K-step
+constexpr int F4_WTILE = 256 * F4_WROW;                  // 16 KiB
+constexpr int F4_STAGE = F4_ATILE + F4_WTILE;
+constexpr int F4_LDS = 2 * F4_STAGE;                     // 96 KiB
+constexpr int F4_BN = 256;
+
+enum { F4_EPI_NONE = 0, F4_EPI_BIAS = 1, F4_EPI_RES = 5, F4_EPI_SWIGLU = 6 };
+enum { F4_DEC_NONE = 0, F4_DEC_BIAS = 1, F4_DEC_RES = 2, F4_DEC_SWIGLU = 3 };
+
+struct Fp4GemmArgs {
+  const uint8_t* A; const uint8_t* W; const uint8_t* E; const float* sa;
+  const void* bias; const void* res; void* out;
+  int M, N, K;
+  int64_t lda, ldw, lde, ldr, ldo;
+  int tiles_m, tiles_n;
+};
+
+__device__ __forceinline__ float silu4(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
+__device__ __forceinline__ float silu4_dec(float x) { return x / (1.0f + __expf(-x)); }
+
+__device__ __forceinline__ void glds16_f4(const void* gsrc, void* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
+                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
+
+__device__ __forceinline__ void tile_of_block4(int bid, int nblocks, int tiles_m, int tiles_n, int& tm, int& tn) {
+  const int q = nblocks >> 3, r = nblocks & 7, xcd = bid & 7;
+  const int L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  constexpr int GROUP_M = 8;
+  const int per_group = GROUP_M * tiles_n;
+  const int g = L / per_group, in_g = L - g * per_group;
+  const int first_m = g * GROUP_M;
+  const int gsz = (tiles_m - first_m) < GROUP_M ? (tiles_m - first_m) : GROUP_M;
+  tm = first_m + in_g % gsz;
+  tn = in_g / gsz;
+}
+
+// weight row of the [N, K] matrix behind row `row` of the 256-row tile.  SwiGLU (tile columns = two groups of [gate64 | up64]):
+// wave column row >> 6 gets the gate columns and the MATCHING up columns of one 32-wide output block (as gemm_fp8_kernel)
+template <int EPI>
+__device__ __forceinline__ int f4_wcol(int row) {
+  return EPI == F4_EPI_SWIGLU ? 128 * (row >> 7) + ((row & 32) ? 64 : 0) + 32 * ((row >> 6) & 1) + (row & 31) : row;
+}
+
+template <typename T, int EPI>
+__global__ __launch_bounds__(512, 2) void gemm_mxfp4_kernel(Fp4GemmArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int MT = 8;
+  constexpr int MG = MT / 4;              // m-tiles per phase (4 phases)
+  constexpr int WROWS = MT * 16;
+  constexpr int BM = 2 * WROWS;
+  constexpr int APW = BM / 8 / 8;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 2, wn = wave & 3;
+  int tm, tn;
+  tile_of_block4(blockIdx.x, gridDim.x, p.tiles_m, p.tiles_n, tm, tn);
+  const int m0 = tm * BM, n0 = tn * F4_BN;
+
+  unsigned a_off[APW], w_off[2];
+#pragma unroll
+  for (int i = 0; i < APW; ++i) {
+    const int row = wave * (APW * 8) + i * 8 + (lane >> 3);
+    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+    int gm = m0 + row;
+    gm = gm < p.M ? gm : p.M - 1;
+    a_off[i] = (unsigned)(gm * (int)p.lda + chunk * 16);
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {           // a DMA of the weight tile = 16 rows x 4 chunks
+    const int row = wave * 32 + i * 16 + (lane >> 2);
+    const int chunk = (lane & 3) ^ ((row >> 2) & 3);
+    w_off[i] = (unsigned)((n0 + f4_wcol<EPI>(row)) * (int)p.ldw + chunk * 16);
+  }
+  auto stage = [&](int buf, int kt) {
+    char* ba = smem + buf * F4_STAGE + (wave * APW * 8) * F4_BK;
+    char* bw = smem + buf * F4_STAGE + F4_ATILE + (wave * 32) * F4_WROW;
+    const char* Ak = (const char*)p.A + (size_t)kt * F4_BK;
+    const char* Wk = (const char*)p.W + (size_t)kt * F4_WROW;
+#pragma unroll
+    for (int i = 0; i < APW; ++i) glds16_f4(Ak + a_off[i], ba + i * 8 * F4_BK);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) glds16_f4(Wk + w_off[i], bw + i * 16 * F4_WROW);
+  };
+
+  // activation fragment = 32 bytes = logical chunks g and 4 + g of the lane's row (g = lane>>4, see the header); weight fragment =
+  // chunk g of its 64-byte row (16 bytes = the 32 codes of MX block g of this K-step)
+  const int l15 = lane & 15, g4 = lane >> 4;
+  const int sw = (lane >> 1) & 7;
+  const int frow = l15 * F4_BK;
+  const unsigned fo_lo = frow + (((g4) ^ sw) << 4), fo_hi = frow + (((g4 + 4) ^ sw) << 4);
+  const unsigned fo_w = l15 * F4_WROW + ((g4 ^ (l15 >> 2)) << 4);
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  const unsigned offA = lds0 + (wm * WROWS) * F4_BK, offW = lds0 + F4_ATILE + (wn * 64) * F4_WROW + fo_w;
+
+  // the lane's block exponent of n-tile ni at K-step kt: e[weight row][4 kt + g]
+  const uint8_t* eptr[4];
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) eptr[ni] = p.E + (int64_t)(n0 + f4_wcol<EPI>(wn * 64 + 16 * ni + l15)) * p.lde + g4;
+
+  f4_f32x4 acc[4][MT];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < MT; ++j) acc[i][j] = f4_f32x4{0.f, 0.f, 0.f, 0.f};
+
+  f4_v4i A0[MG][2], A1[MG][2], B0[4];
+  int sc[4], scn[4];
+#define F4_DSR(dst, addr, imm) asm volatile("ds_read_b128 %0, %1 offset:" #imm : "=v"(dst) : "v"(addr))
+#define F4_RDT(f, lo, hi, imm) { F4_DSR(f[0], lo, imm); F4_DSR(f[1], hi, imm); }
+#define F4_RD_A(F, lo, hi, tile0)                                                                                 \
+  {                                                                                                               \
+    if constexpr ((tile0) == 0) { F4_RDT(F[0], lo, hi, 0); F4_RDT(F[1], lo, hi, 2048); }                          \
+    else if constexpr ((tile0) == 2) { F4_RDT(F[0], lo, hi, 4096); F4_RDT(F[1], lo, hi, 6144); }                  \
+    else if constexpr ((tile0) == 4) { F4_RDT(F[0], lo, hi, 8192); F4_RDT(F[1], lo, hi, 10240); }                 \
+    else { F4_RDT(F[0], lo, hi, 12288); F4_RDT(F[1], lo, hi, 14336); }                                            \
+  }
+#define F4_RD_B(F, w) { F4_DSR(F[0], w, 0); F4_DSR(F[1], w, 1024); F4_DSR(F[2], w, 2048); F4_DSR(F[3], w, 3072); }
+#define F4_WA(cnt, F) asm volatile("s_waitcnt " cnt : "+v"(F[0][0]), "+v"(F[0][1]), "+v"(F[1][0]), "+v"(F[1][1]) : : "memory")
+#define F4_WAB(cnt, F, G)                                                                                          \
+  asm volatile("s_waitcnt " cnt : "+v"(F[0][0]), "+v"(F[0][1]), "+v"(F[1][0]), "+v"(F[1][1]), "+v"(G[0]), "+v"(G[1]), \
+               "+v"(G[2]), "+v"(G[3]) : : "memory")
+#define F4_FRAG(f) (f4_v8i{f[0][0], f[0][1], f[0][2], f[0][3], f[1][0], f[1][1], f[1][2], f[1][3]})
+#define F4_FRAGW(f) (__builtin_shufflevector(f, f, 0, 1, 2, 3, -1, -1, -1, -1))
+#define F4_MMA(FA, FB, tile0)                                                                                       \
+  {                                                                                                                 \
+    __builtin_amdgcn_s_setprio(1);                                                                                  \
+    _Pragma("unroll") for (int i = 0; i < MG; ++i)                                                                  \
+    _Pragma("unroll") for (int ni = 0; ni < 4; ++ni)                                                                \
+        acc[ni][(tile0) + i] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(F4_FRAGW(FB[ni]), F4_FRAG(FA[i]),   \
+                                                                                  acc[ni][(tile0) + i], 4, 0, 0, sc[ni], 0, 127); \
+    __builtin_amdgcn_s_setprio(0);                                                                                  \
+  }
+
+  const int nt = p.K / F4_BK;
+  stage(0, 0);
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) sc[ni] = eptr[ni][0];
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  for (int t = 0; t < nt; ++t) {
+    const int cur = t & 1;
+    const unsigned alo = offA + cur * F4_STAGE + fo_lo, ahi = offA + cur * F4_STAGE + fo_hi;
+    const unsigned wad = offW + cur * F4_STAGE;
+    F4_RD_B(B0, wad);
+    F4_RD_A(A0, alo, ahi, 0);
+    if (t + 1 < nt) {                                // buffer cur^1 was released by the barrier that ended step t-1
+      stage(cur ^ 1, t + 1);
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) scn[ni] = eptr[ni][4 * (t + 1)];
+    }
+    F4_RD_A(A1, alo, ahi, 2);
+    F4_WAB("lgkmcnt(4)", A0, B0);
+    F4_MMA(A0, B0, 0);
+    F4_RD_A(A0, alo, ahi, 4);
+    F4_WA("lgkmcnt(4)", A1);
+    F4_MMA(A1, B0, 2);
+    F4_RD_A(A1, alo, ahi, 6);
+    F4_WA("lgkmcnt(4)", A0);
+    F4_MMA(A0, B0, 4);
+    F4_WA("vmcnt(0) lgkmcnt(0)", A1);               // last fragments + this wave's share of tile t+1 and its exponents
+    F4_MMA(A1, B0, 6);
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) sc[ni] = scn[ni];
+    __builtin_amdgcn_s_barrier();                    // tile t fully read by everyone, tile t+1 visible
+  }
+  __syncthreads();
+
+  // epilogue as gemm_fp8_kernel (the block scales are already inside the accumulators: only sa[m] is left): each wave turns its
+  // 128 x 64 part of the C tile around in a private 8 KiB of LDS, 32 rows at a time; SwiGLU formed in registers first
+  const T* bias = (const T*)p.bias;
+  T* out = (T*)p.out;
+  {
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    const int e15 = ln & 15, l4 = ln >> 4;
+    char* const reg = smem + wave * 8192;
+    if constexpr (EPI == F4_EPI_SWIGLU) {
+      constexpr int CP = 80;
+      const int rrow = ln >> 2, rch = ln & 3;
+      T* const obase = out + tn * 128 + (wn >> 1) * 64 + (wn & 1) * 32 + rch * 8;
+#pragma unroll
+      for (int q = 0; q < MT / 2; ++q) {
+#pragma unroll
+        for (int m2 = 0; m2 < 2; ++m2) {
+          const int mi = 2 * q + m2;
+          int gmc = m0 + wm * WROWS + 16 * mi + e15;
+          gmc = gmc < p.M ? gmc : p.M - 1;
+          const float sa = p.sa[gmc];
+#pragma unroll
+          for (int n2 = 0; n2 < 2; ++n2) {
+            float v[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              v[r] = round_to<T>(silu4(round_to<T>(acc[n2][mi][r] * sa))) * round_to<T>(acc[2 + n2][mi][r] * sa);
+            uint2 pk;
+            pk.x = pack2<T>(v[0], v[1]); pk.y = pack2<T>(v[2], v[3]);
+            *reinterpret_cast<uint2*>(reg + (m2 * 16 + e15) * CP + (16 * n2 + 4 * l4) * 2) = pk;
+          }
+        }
+        uint4 cq[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) cq[j] = *reinterpret_cast<const uint4*>(reg + (rrow + 16 * j) * CP + rch * 16);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int gm = m0 + wm * WROWS + 32 * q + rrow + 16 * j;
+          if (gm < p.M) *reinterpret_cast<uint4*>(obase + (int64_t)gm * p.ldo) = cq[j];
+        }
+      }
+    } else {
+      constexpr int CP = 144;
+      const int rrow = ln >> 3, rch = ln & 7;
+      const int colr = n0 + wn * 64 + rch * 8;
+      float bv[4][4];
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int c = n0 + wn * 64 + 16 * ni + 4 * l4 + r;
+          bv[ni][r] = bias != nullptr ? to_f32(bias[c]) : 0.f;
+        }
+#pragma unroll
+      for (int q = 0; q < MT / 2; ++q) {
+        uint4 rr[4];
+        if constexpr (EPI == F4_EPI_RES) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            int gc = m0 + wm * WROWS + 32 * q + rrow + 8 * j;
+            gc = gc < p.M ? gc : p.M - 1;
+            rr[j] = *reinterpret_cast<const uint4*>((const T*)p.res + (int64_t)gc * p.ldr + colr);
+          }
+        }
+#pragma unroll
+        for (int m2 = 0; m2 < 2; ++m2) {
+          const int mi = 2 * q + m2;
+          int gmc = m0 + wm * WROWS + 16 * mi + e15;
+          gmc = gmc < p.M ? gmc : p.M - 1;
+          const float sa = p.sa[gmc];
+#pragma unroll
+          for (int ni = 0; ni < 4; ++ni) {
+            uint2 pk;
+            pk.x = pack2<T>(acc[ni][mi][0] * sa + bv[ni][0], acc[ni][mi][1] * sa + bv[ni][1]);
+            pk.y = pack2<T>(acc[ni][mi][2] * sa + bv[ni][2], acc[ni][mi][3] * sa + bv[ni][3]);
+            *reinterpret_cast<uint2*>(reg + (m2 * 16 + e15) * CP + (16 * ni + 4 * l4) * 2) = pk;
+          }
+        }
+        uint4 cq[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cq[j] = *reinterpret_cast<const uint4*>(reg + (rrow + 8 * j) * CP + rch * 16);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          uint4 c = cq[j];
+          const int gm = m0 + wm * WROWS + 32 * q + rrow + 8 * j;
+          if constexpr (EPI == F4_EPI_RES) {
+            float v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = vec_get<T>(c, e) + vec_get<T>(rr[j], e);
+            c = vec_pack<T>(v);
+          }
+          if (gm < p.M) *reinterpret_cast<uint4*>(out + (int64_t)gm * p.ldo + colr) = c;
+        }
+      }
+    }
+  }
+#undef F4_DSR
+#undef F4_RDT
+#undef F4_RD_A
+#undef F4_RD_B
+#undef F4_WA
+#undef F4_WAB
+#undef F4_FRAG
+#undef F4_FRAGW
+#undef F4_MMA
+}
+
+// MXFP4 quantiser.  Per block of 32 k: e = clamp(floor(log2(amax)) - 2 + 127, 0, 254) (127 for an all-zero block) - for a finite
+// 16-bit input that is the f32 exponent field of amax minus 2, clamped below; elements are w * 2^(127 - e) (exact) rounded to
+// the nearest of {0, .5, 1, 1.5, 2, 3, 4, 6} with ties to the even code, saturating at 6; a code of magnitude zero carries no
+// sign.  One lane = 8 elements = 4 code bytes; the 4 lanes of a block share its amax.
+__device__ __forceinline__ uint32_t f4_code(float w, float mul) {
+  const float v = fabsf(w) * mul;
+  const uint32_t c = (uint32_t)(v > 0.25f) + (uint32_t)(v >= 0.75f) + (uint32_t)(v > 1.25f) + (uint32_t)(v >= 1.75f) + (uint32_t)(v > 2.5f) +
+                     (uint32_t)(v >= 3.5f) + (uint32_t)(v > 5.0f);
+  return (c != 0 && w < 0.f) ? (c | 8u) : c;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void quantize_mxfp4_kernel(const T* __restrict__ x, int64_t ldx, int64_t rows, int cols, uint8_t* __restrict__ q,
+                                                             int64_t ldq, uint8_t* __restrict__ e, int64_t lde) {
+  const int nv = cols / 8;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= rows * nv) return;                      // nv % 4 == 0: the four lanes of a block leave together
+  const int64_t row = t / nv;
+  const int c = (int)(t - row * nv);
+  const uint4 v = reinterpret_cast<const uint4*>(x + row * ldx)[c];
+  float f[8], amax = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { f[j] = vec_get<T>(v, j); amax = fmaxf(amax, fabsf(f[j])); }
+  amax = fmaxf(amax, __shfl_xor(amax, 1));
+  amax = fmaxf(amax, __shfl_xor(amax, 2));
+  int ex = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 2;
+  ex = ex < 0 ? 0 : ex;
+  if (amax == 0.f) ex = 127;
+  // 2^(127 - ex): exponent field 254 - ex, and 2^-127 (ex = 254, unreachable from a finite 16-bit input) as a subnormal
+  const float mul = __uint_as_float(ex < 254 ? (uint32_t)(254 - ex) << 23 : 0x00400000u);
+  uint32_t word = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) word |= f4_code(f[j], mul) << (4 * j);
+  reinterpret_cast<uint32_t*>(q + row * ldq)[c] = word;
+  if ((c & 3) == 0) e[row * lde + (c >> 2)] = (uint8_t)ex;
+}
+
+// ---- decode linears (W4A16) ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint4 ldg_nt4(const uint4* p) {
+  uint4 r;
+  r.x = __builtin_nontemporal_load(&p->x);
+  r.y = __builtin_nontemporal_load(&p->y);
+  r.z = __builtin_nontemporal_load(&p->z);
+  r.w = __builtin_nontemporal_load(&p->w);
+  return r;
+}
+__device__ __forceinline__ float f4_scale(uint32_t e) { return __uint_as_float(e << 23); }     // only the exponent field is read
+
+// 8 codes (one 32-bit word, k ascending from the low nibble) times 2^(e-127), as 8 values of the activation type
+__device__ __forceinline__ uint4 f4_widen8(bf16_t, uint32_t w, float sc) {
+  typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+  const b2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 0), p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 1);
+  const b2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 2), p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 3);
+  return make_uint4(__builtin_bit_cast(uint32_t, p0), __builtin_bit_cast(uint32_t, p1), __builtin_bit_cast(uint32_t, p2), __builtin_bit_cast(uint32_t, p3));
+}
+__device__ __forceinline__ uint4 f4_widen8(f16_t, uint32_t w, float sc) {
+  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+  const h2 p0 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 0), p1 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 1);
+  const h2 p2 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 2), p3 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 3);
+  return make_uint4(__builtin_bit_cast(uint32_t, p0), __builtin_bit_cast(uint32_t, p1), __builtin_bit_cast(uint32_t, p2), __builtin_bit_cast(uint32_t, p3));
+}
+
+using f4_bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using f4_f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+__device__ __forceinline__ f4_f32x4 f4_mfma16(bf16_t, const uint4& a, const uint4& b, f4_f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(f4_bf16x8, a), __builtin_bit_cast(f4_bf16x8, b), c, 0, 0, 0);
+}
+__device__ __forceinline__ f4_f32x4 f4_mfma16(f16_t, const uint4& a, const uint4& b, f4_f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f4_f16x8, a), __builtin_bit_cast(f4_f16x8, b), c, 0, 0, 0);
+}
+
+// VALU form (one row; up to 4 rows for shapes without a matrix-core form): linear_decode_fp8_kernel over 4-bit codes.  Workgroup =
+// 4 waves = FOUR weight rows, K split over the 256 threads in 16-byte chunks = 32 weights = exactly one MX block; the codes are
+// widened to f32 with their block scale by v_cvt_scalef32_pk_f32_fp4 (exact).  Each activation row's arithmetic is the M = 1
+// arithmetic, so batching never changes a result bit.
+template <typename T, int EPI, int M>
+__global__ __launch_bounds__(256, 4) void linear_decode_mxfp4_kernel(
+    const T* __restrict__ x, int64_t ldx, const uint8_t* __restrict__ W, int64_t ldw, const uint8_t* __restrict__ E, int64_t lde,
+    const T* __restrict__ bias, const T* __restrict__ res, int64_t ldr, T* __restrict__ out, int64_t ldo, int N, int K) {
+  __shared__ float red[M][4][4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int kv = K / 32;
+  int rows[4];
+  int o0;
+  if (EPI == F4_DEC_SWIGLU) {
+    o0 = blockIdx.x * 2;
+    rows[0] = (o0 >> 6) * 128 + (o0 & 63); rows[1] = rows[0] + 64;
+    rows[2] = ((o0 + 1) >> 6) * 128 + ((o0 + 1) & 63); rows[3] = rows[2] + 64;
+  } else {
+    o0 = blockIdx.x * 4;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) rows[r] = o0 + r;
+  }
+  float s[M][4];
+#pragma unroll
+  for (int m = 0; m < M; ++m)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) s[m][r] = 0.f;
+  const uint4* wr[4];
+  const uint8_t* er[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) { wr[r] = reinterpret_cast<const uint4*>(W + (int64_t)rows[r] * ldw); er[r] = E + (int64_t)rows[r] * lde; }
+  for (int k = tid; k < kv; k += 256) {
+    uint4 w4[4];
+    float sc[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { w4[r] = ldg_nt4(wr[r] + k); sc[r] = f4_scale(__builtin_nontemporal_load(er[r] + k)); }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {                   // 8 weights of each row against 8 activations of each activation row
+      uint4 xv[M];
+#pragma unroll
+      for (int m = 0; m < M; ++m) xv[m] = reinterpret_cast<const uint4*>(x + m * ldx)[4 * k + q];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t ww = q == 0 ? w4[r].x : q == 1 ? w4[r].y : q == 2 ? w4[r].z : w4[r].w;
+        const f4_f32x2 c0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(ww, sc[r], 0), c1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(ww, sc[r], 1);
+        const f4_f32x2 c2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(ww, sc[r], 2), c3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(ww, sc[r], 3);
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+          s[m][r] = fmaf(c0[0], vec_get<T>(xv[m], 0), s[m][r]);
+          s[m][r] = fmaf(c0[1], vec_get<T>(xv[m], 1), s[m][r]);
+          s[m][r] = fmaf(c1[0], vec_get<T>(xv[m], 2), s[m][r]);
+          s[m][r] = fmaf(c1[1], vec_get<T>(xv[m], 3), s[m][r]);
+          s[m][r] = fmaf(c2[0], vec_get<T>(xv[m], 4), s[m][r]);
+          s[m][r] = fmaf(c2[1], vec_get<T>(xv[m], 5), s[m][r]);
+          s[m][r] = fmaf(c3[0], vec_get<T>(xv[m], 6), s[m][r]);
+          s[m][r] = fmaf(c3[1], vec_get<T>(xv[m], 7), s[m][r]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < M; ++m)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) s[m][r] += __shfl_xor(s[m][r], off);
+    }
+  if (lane == 0) {
+#pragma unroll
+    for (int m = 0; m < M; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[m][r][wave] = s[m][r];
+  }
+  __syncthreads();
+  if (EPI == F4_DEC_SWIGLU) {
+    if (tid < 2 * M) {
+      const int m = tid >> 1, t2 = tid & 1;
+      const float g = round_to<T>(red[m][2 * t2][0] + red[m][2 * t2][1] + red[m][2 * t2][2] + red[m][2 * t2][3]);
+      const float u = round_to<T>(red[m][2 * t2 + 1][0] + red[m][2 * t2 + 1][1] + red[m][2 * t2 + 1][2] + red[m][2 * t2 + 1][3]);
+      out[m * ldo + o0 + t2] = from_f32<T>(round_to<T>(silu4_dec(g)) * u);
+    }
+  } else if (tid < 4 * M) {
+    const int m = tid >> 2, r = tid & 3;
+    const int n = o0 + r;
+    float v = red[m][r][0] + red[m][r][1] + red[m][r][2] + red[m][r][3];
+    if (EPI == F4_DEC_BIAS) v += to_f32(bias[n]);
+    v = round_to<T>(v);
+    if (EPI == F4_DEC_RES) v += to_f32(res[m * ldr + n]);
+    out[m * ldo + n] = from_f32<T>(v);
+  }
+}
+
+// Matrix-core form (2..32 rows), as linear_decode_fp8_mfma_kernel: a workgroup owns 16 outputs (SwiGLU: 16 gate + 16 up rows), its 8
+// waves split K in tiles of 256.  A tile is 16 rows x 128 BYTES of codes, loaded with full-line coalescing (2 x 16 bytes per lane)
+// into the wave-private LDS tile, plus the 8 block exponents of the lane's row (one 8-byte load); the fragment of a k step is
+// 4 bytes per lane = 8 codes, widened with the block scale to the activation type by v_cvt_scalef32_pk_{bf16,f16}_fp4 (exact)
+// and fed to v_mfma_f32_16x16x32 against the 16-bit activation rows.  Column m of the result depends on row m of x only.
+template <typename T, int EPI, int MB>
+__global__ __launch_bounds__(512) void linear_decode_mxfp4_mfma_kernel(const T* __restrict__ x, int64_t ldx, int M, const uint8_t* __restrict__ W,
+                                                                       int64_t ldw, const uint8_t* __restrict__ E, int64_t lde,
+                                                                       const T* __restrict__ bias, const T* __restrict__ res, int64_t ldr,
+                                                                       T* __restrict__ out, int64_t ldo, int N, int K) {
+  constexpr int RG = EPI == F4_DEC_SWIGLU ? 2 : 1;
+  constexpr int PITCH = 144;
+  __shared__ __attribute__((aligned(16))) char tile[8][RG][16 * PITCH];
+  __shared__ float part[8][RG][MB][256];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int lr = lane >> 3, lc = lane & 7;
+  const int o0 = blockIdx.x * 16;
+  int row0[RG];
+  if (EPI == F4_DEC_SWIGLU) { row0[0] = (o0 >> 6) * 128 + (o0 & 63); row0[RG - 1] = row0[0] + 64; }
+  else row0[0] = o0;
+  const uint8_t* wbase[RG];
+  const uint8_t* ebase[RG];
+#pragma unroll
+  for (int q = 0; q < RG; ++q) {
+    wbase[q] = W + (int64_t)(row0[q] + lr) * ldw + 16 * lc;
+    ebase[q] = E + (int64_t)(row0[q] + r) * lde;
+  }
+  bool col_ok[MB];
+  const T* xrow[MB];
+#pragma unroll
+  for (int b = 0; b < MB; ++b) {
+    col_ok[b] = r + 16 * b < M;
+    xrow[b] = x + (int64_t)(col_ok[b] ? r + 16 * b : 0) * ldx + 8 * g;
+  }
+  f4_f32x4 acc[RG][MB];
+#pragma unroll
+  for (int q = 0; q < RG; ++q)
+#pragma unroll
+    for (int b = 0; b < MB; ++b) acc[q][b] = f4_f32x4{0.f, 0.f, 0.f, 0.f};
+  const int tiles = K / 256;
+  for (int s = wave; s < tiles; s += 8) {
+    const int k0 = 256 * s;
+    uint4 wreg[RG][2], xb[MB][8];
+    uint32_t ex[RG][2];
+#pragma unroll
+    for (int q = 0; q < RG; ++q) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) wreg[q][j] = ldg_nt4(reinterpret_cast<const uint4*>(wbase[q] + (int64_t)(8 * j) * ldw + k0 / 2));
+      const uint32_t* ep = reinterpret_cast<const uint32_t*>(ebase[q] + k0 / 32);
+      ex[q][0] = __builtin_nontemporal_load(ep); ex[q][1] = __builtin_nontemporal_load(ep + 1);
+    }
+#pragma unroll
+    for (int b = 0; b < MB; ++b)
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        xb[b][t] = make_uint4(0u, 0u, 0u, 0u);
+        if (col_ok[b]) xb[b][t] = *reinterpret_cast<const uint4*>(xrow[b] + k0 + 32 * t);
+      }
+#pragma unroll
+    for (int q = 0; q < RG; ++q)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        *reinterpret_cast<uint4*>(&tile[wave][q][(8 * j + lr) * PITCH + lc * 16]) = wreg[q][j];
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+#pragma unroll
+      for (int q = 0; q < RG; ++q) {
+        const uint32_t w4 = *reinterpret_cast<const uint32_t*>(&tile[wave][q][r * PITCH + (4 * t + g) * 4]);
+        const uint4 a = f4_widen8(T{}, w4, f4_scale((ex[q][t >> 2] >> (8 * (t & 3))) & 0xffu));
+#pragma unroll
+        for (int b = 0; b < MB; ++b) acc[q][b] = f4_mfma16(T{}, a, xb[b][t], acc[q][b]);
+      }
+  }
+#pragma unroll
+  for (int q = 0; q < RG; ++q)
+#pragma unroll
+    for (int b = 0; b < MB; ++b)
+      *reinterpret_cast<float4*>(&part[wave][q][b][lane * 4]) = make_float4(acc[q][b][0], acc[q][b][1], acc[q][b][2], acc[q][b][3]);
+  __syncthreads();
+  for (int e = tid; e < 256 * MB; e += 512) {
+    const int b = e >> 8, t8 = e & 255;
+    const int l = t8 >> 2, i = t8 & 3;
+    const int row = 4 * (l >> 4) + i, m = (l & 15) + 16 * b;
+    float v[RG];
+#pragma unroll
+    for (int q = 0; q < RG; ++q) {
+      v[q] = 0.f;
+#pragma unroll
+      for (int w = 0; w < 8; ++w) v[q] += part[w][q][b][t8];
+    }
+    if (m < M) {
+      const int n = o0 + row;
+      if (EPI == F4_DEC_SWIGLU) {
+        const float gt = round_to<T>(v[0]), up = round_to<T>(v[RG - 1]);
+        out[m * ldo + n] = from_f32<T>(round_to<T>(silu4_dec(gt)) * up);
+      } else {
+        float y = v[0];
+        if (EPI == F4_DEC_BIAS) y += to_f32(bias[n]);
+        y = round_to<T>(y);
+        if (EPI == F4_DEC_RES) y += to_f32(res[m * ldr + n]);
+        out[m * ldo + n] = from_f32<T>(y);
+      }
+    }
+  }
+}
+
+template <typename T>
+static int launch_mxfp4(Fp4GemmArgs p, int epi, hipStream_t st) {
+  p.tiles_m = (p.M + 255) / 256;
+  p.tiles_n = p.N / F4_BN;
+#define F4_CASE(E)                                                                                        \
+  case E: {                                                                                               \
+    auto k = gemm_mxfp4_kernel<T, E>;                                                                     \
+    static bool attr_done = false;                                                                        \
+    if (!attr_done) {                                                                                     \
+      hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, F4_LDS); \
+      if (e != hipSuccess) { set_error("v3d_gemm_mxfp4: LDS attribute: %s", hipGetErrorString(e)); return V3D_E_LAUNCH; } \
+      attr_done = true;                                                                                   \
+    }                                                                                                     \
+    hipLaunchKernelGGL(k, dim3(p.tiles_m * p.tiles_n), dim3(512), F4_LDS, st, p);                         \
+  } break;
+  switch (epi) {
+    F4_CASE(F4_EPI_NONE)
+    F4_CASE(F4_EPI_BIAS)
+    F4_CASE(F4_EPI_RES)
+    F4_CASE(F4_EPI_SWIGLU)
+    default: set_error("v3d_gemm_mxfp4: epilogue %d unsupported (NONE, BIAS, RES, SWIGLU)", epi); return V3D_E_INVALID;
+  }
+#undef F4_CASE
+  return check_launch("v3d_gemm_mxfp4");
+}
+
+}  // namespace v3d
+
+using namespace v3d;
+
+extern "C" int v3d_quantize_mxfp4_rows(const void* w, int64_t ldw, int64_t rows, int cols, int dtype, void* q, int64_t ldq, void* e,
+                                       int64_t lde, void* stream) {
+  V3D_REQUIRE(w && q && e, "v3d_quantize_mxfp4_rows: null pointer");
+  V3D_REQUIRE(rows >= 0 && cols > 0 && cols % 128 == 0, "v3d_quantize_mxfp4_rows: cols=%d must be a multiple of 128", cols);
+  V3D_REQUIRE(ldw % 8 == 0 && ldw >= cols && ldq % 4 == 0 && ldq >= cols / 2 && lde >= cols / 32, "v3d_quantize_mxfp4_rows: leading dimensions");
+  V3D_REQUIRE(aligned16(w) && (reinterpret_cast<uintptr_t>(q) & 3) == 0, "v3d_quantize_mxfp4_rows: alignment");
+  if (rows == 0) return V3D_OK;
+  const int64_t threads = rows * (cols / 8);
+  V3D_REQUIRE((threads + 255) / 256 < (1ll << 31), "v3d_quantize_mxfp4_rows: matrix too large");
+  const unsigned blocks = (unsigned)((threads + 255) / 256);
+  if (dtype == V3D_BF16) hipLaunchKernelGGL(quantize_mxfp4_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)w, ldw, rows, cols, (uint8_t*)q, ldq, (uint8_t*)e, lde);
+  else if (dtype == V3D_F16) hipLaunchKernelGGL(quantize_mxfp4_kernel<f16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const f16_t*)w, ldw, rows, cols, (uint8_t*)q, ldq, (uint8_t*)e, lde);
+  else { set_error("v3d_quantize_mxfp4_rows: dtype must be f16 or bf16"); return V3D_E_INVALID; }
+  return check_launch("v3d_quantize_mxfp4_rows");
+}
+
+extern "C" int v3d_gemm_mxfp4(const void* A, int64_t lda, const float* scale_a, const void* Wq, int64_t ldw, const void* We, int64_t lde,
+                              const void* bias, const void* res, int64_t ldr, void* out, int64_t ldo, int M, int N, int K, int out_dtype,
+                              int epilogue, void* stream) {
+  V3D_REQUIRE(A && Wq && We && scale_a && out, "v3d_gemm_mxfp4: null pointer");
+  V3D_REQUIRE(out_dtype == V3D_F16 || out_dtype == V3D_BF16, "v3d_gemm_mxfp4: output dtype must be f16 or bf16");
+  V3D_REQUIRE(M > 0 && N > 0 && K > 0 && N % F4_BN == 0 && K % F4_BK == 0, "v3d_gemm_mxfp4: N=%d must be a multiple of 256 and K=%d of 128", N, K);
+  V3D_REQUIRE(lda >= K && ldw >= K / 2 && lde >= K / 32 && lda % 16 == 0 && ldw % 16 == 0 && ldo % 8 == 0, "v3d_gemm_mxfp4: leading dimensions");
+  V3D_REQUIRE(aligned16(A) && aligned16(Wq) && aligned16(out), "v3d_gemm_mxfp4: pointers must be 16-byte aligned");
+  V3D_REQUIRE((int64_t)M * lda < (1ll << 31) && (int64_t)N * ldw < (1ll << 31), "v3d_gemm_mxfp4: operand larger than 2 GiB");
+  V3D_REQUIRE(epilogue != F4_EPI_BIAS || bias, "v3d_gemm_mxfp4: bias epilogue without bias");
+  V3D_REQUIRE(epilogue != F4_EPI_RES || (res && aligned16(res) && ldr % 8 == 0), "v3d_gemm_mxfp4: residual epilogue without residual");
+  Fp4GemmArgs p;
+  p.A = (const uint8_t*)A; p.W = (const uint8_t*)Wq; p.E = (const uint8_t*)We; p.sa = scale_a;
+  p.bias = epilogue == F4_EPI_BIAS ? bias : nullptr; p.res = epilogue == F4_EPI_RES ? res : nullptr; p.out = out;
+  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.lde = lde; p.ldr = ldr; p.ldo = ldo;
+  hipStream_t st = (hipStream_t)stream;
+  return out_dtype == V3D_BF16 ? launch_mxfp4<bf16_t>(p, epilogue, st) : launch_mxfp4<f16_t>(p, epilogue, st);
+}
+
+extern "C" int v3d_linear_decode_mxfp4_rows(const void* x, int64_t ldx, int M, const void* Wq, int64_t ldw, const void* We, int64_t lde,
+                                            const void* bias, const void* res, int64_t ldr, void* out, int64_t ldo, int N, int K, int dtype,
+                                            int epilogue, void* stream) {
+  const char* who = "v3d_linear_decode_mxfp4_rows";
+  V3D_REQUIRE(x && Wq && We && out, "%s: null pointer", who);
+  V3D_REQUIRE(dtype == V3D_F16 || dtype == V3D_BF16, "%s: dtype must be f16 or bf16", who);
+  V3D_REQUIRE(N > 0 && K > 0 && K % 128 == 0 && ldw % 16 == 0 && ldw >= K / 2 && lde >= K / 32, "%s: bad shape N=%d K=%d", who, N, K);
+  // one row: VALU form; 2..32 rows: matrix-core form when the shape allows (a row's bits then depend neither on the other rows
+  // nor on M); other shapes: VALU form with up to 4 rows
+  const bool mfma_ok = K % 256 == 0 && lde % 8 == 0 && (reinterpret_cast<uintptr_t>(We) & 7) == 0 &&
+                       (epilogue == F4_DEC_SWIGLU ? N % 128 == 0 : N % 16 == 0);
+  const bool mfma = mfma_ok && M >= 2;
+  V3D_REQUIRE(M >= 1 && M <= (mfma_ok ? 32 : 4), "%s: 1 to %d activation rows for this shape (got %d)", who, mfma_ok ? 32 : 4, M);
+  V3D_REQUIRE(N % 4 == 0 && (epilogue != F4_DEC_SWIGLU || N % 128 == 0), "%s: N=%d not supported", who, N);
+  V3D_REQUIRE(aligned16(x) && aligned16(Wq) && (M == 1 || (ldx % 8 == 0 && ldx >= K)), "%s: alignment", who);
+  V3D_REQUIRE(epilogue != F4_DEC_BIAS || bias, "%s: bias epilogue without bias", who);
+  V3D_REQUIRE(epilogue != F4_DEC_RES || res, "%s: residual epilogue without residual", who);
+  hipStream_t st = (hipStream_t)stream;
+  if (mfma) {
+    const int mblocks = (epilogue == F4_DEC_SWIGLU ? N / 2 : N) / 16;
+#define V3D_LD4M_B(TT, EE, BB) hipLaunchKernelGGL((linear_decode_mxfp4_mfma_kernel<TT, EE, BB>), dim3(mblocks), dim3(512), 0, st, (const TT*)x, ldx, M, \
+                                                  (const uint8_t*)Wq, ldw, (const uint8_t*)We, lde, (const TT*)bias, (const TT*)res, ldr, (TT*)out, ldo, N, K)
+#define V3D_LD4M(TT, EE) { if (M <= 16) V3D_LD4M_B(TT, EE, 1); else V3D_LD4M_B(TT, EE, 2); }
+#define V3D_LD4M_E(TT)                                                                                \
+  switch (epilogue) {                                                                                 \
+    case F4_DEC_NONE: V3D_LD4M(TT, F4_DEC_NONE); break; case F4_DEC_BIAS: V3D_LD4M(TT, F4_DEC_BIAS); break; \
+    case F4_DEC_RES: V3D_LD4M(TT, F4_DEC_RES); break; case F4_DEC_SWIGLU: V3D_LD4M(TT, F4_DEC_SWIGLU); break; \
+    default: set_error("%s: unknown epilogue %d", who, epilogue); return V3D_E_INVALID;               \
+  }
+    if (dtype == V3D_BF16) { V3D_LD4M_E(bf16_t) } else { V3D_LD4M_E(f16_t) }
+#undef V3D_LD4M_E
+#undef V3D_LD4M
+#undef V3D_LD4M_B
+    return check_launch(who);
+  }
+  const int blocks = N / 4;
+#define V3D_LD4(TT, EE, MM)                                                                                                   \
+  hipLaunchKernelGGL((linear_decode_mxfp4_kernel<TT, EE, MM>), dim3(blocks), dim3(256), 0, st, (const TT*)x, ldx, (const uint8_t*)Wq, ldw, \
+                     (const uint8_t*)We, lde, (const TT*)bias, (const TT*)res, ldr, (TT*)out, ldo, N, K)
+#define V3D_LD4_M(TT, EE)                                                                             \
+  switch (M) { case 1: V3D_LD4(TT, EE, 1); break; case 2: V3D_LD4(TT, EE, 2); break;                  \
+               case 3: V3D_LD4(TT, EE, 3); break; default: V3D_LD4(TT, EE, 4); break; }
+#define V3D_LD4_E(TT)                                                                                 \
+  switch (epilogue) {                                                                                 \
+    case F4_DEC_NONE: V3D_LD4_M(TT, F4_DEC_NONE) break; case F4_DEC_BIAS: V3D_LD4_M(TT, F4_DEC_BIAS) break; \
+    case F4_DEC_RES: V3D_LD4_M(TT, F4_DEC_RES) break; case F4_DEC_SWIGLU: V3D_LD4_M(TT, F4_DEC_SWIGLU) break; \
+    default: set_error("%s: unknown epilogue %d", who, epilogue); return V3D_E_INVALID;               \
+  }
+  if (dtype == V3D_BF16) { V3D_LD4_E(bf16_t) } else { V3D_LD4_E(f16_t) }
+#undef V3D_LD4_E
+#undef V3D_LD4_M
+#undef V3D_LD4
+  return check_launch(who);
+}

@@ -60,7 +60,7 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
     _GENERATE_KW = {"max_new_tokens", "do_sample", "num_beams", "temperature", "top_p", "top_k", "use_cache", "attention_mask",
                     "position_ids", "stopping_criteria", "eos_token_id", "pad_token_id", "video_dict", "max_length"}
 
-    def __init__(self, config, state_dict=None, dtype=torch.float16, device=None, llm_fp8=False, max_frames=32):
+    def __init__(self, config, state_dict=None, dtype=torch.float16, device=None, llm_fp8=False, max_frames=32, llm_fp4=False):
         super().__init__()
         if state_dict is None:
             raise V3DError("LlavaQwenForCausalLM(config) without weights: construct it with from_pretrained(checkpoint_dir) "
@@ -70,7 +70,7 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
         device = _device_of(device)
         self.config = config
         self.engine = Engine(loader.engine_config(config, state_dict), state_dict, dtype=dtype, device=device, max_frames=max_frames,
-                             llm_fp8=llm_fp8)
+                             llm_fp8=llm_fp8, llm_fp4=llm_fp4)
         self._device, self._dtype = device, dtype
         self.ground_head_type = getattr(config, "ground_head_type", None)
         if self.ground_head_type not in (None, "infonce", "mlp", "score"):                      # llava_qwen.py:57-104
@@ -82,12 +82,12 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
     # ------------------------------------------------------------------ loading (builder.py:206-228)
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, config=None, torch_dtype=None, dtype=None, device_map=None,
-                        low_cpu_mem_usage=None, attn_implementation=None, llm_fp8=False, max_frames=32, **kwargs):
+                        low_cpu_mem_usage=None, attn_implementation=None, llm_fp8=False, max_frames=32, llm_fp4=False, **kwargs):
         """low_cpu_mem_usage / attn_implementation are accepted and have no effect here (weights go straight to HBM; attention
         is the engine's flash kernel whatever the name says).  Quantised / sharded-device loading is refused."""
         for k in ("load_in_8bit", "load_in_4bit", "quantization_config"):
             if kwargs.pop(k, None):
-                raise NotImplementedError(f"{k}: bitsandbytes quantisation is outside the accelerated path (use llm_fp8=True for e4m3 weights)")
+                raise NotImplementedError(f"{k}: bitsandbytes quantisation is outside the accelerated path (use llm_fp8=True for e4m3 or llm_fp4=True for MXFP4 weights)")
         if model_args or kwargs:
             raise TypeError(f"LlavaQwenForCausalLM.from_pretrained: unsupported arguments {list(model_args) + sorted(kwargs)}")
         path = os.fspath(pretrained_model_name_or_path)
@@ -119,7 +119,7 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
                 raise V3DError(f"config.vocab_size {vocab} exceeds the checkpoint's {sd['lm_head.weight'].shape[0]} rows")
             sd["lm_head.weight"] = sd["lm_head.weight"][:vocab]
             sd["model.embed_tokens.weight"] = sd["model.embed_tokens.weight"][:vocab]
-        model = cls(config, sd, dtype=dt, device=device_map, llm_fp8=llm_fp8, max_frames=max_frames)
+        model = cls(config, sd, dtype=dt, device=device_map, llm_fp8=llm_fp8, max_frames=max_frames, llm_fp4=llm_fp4)
         gen = os.path.join(path, "generation_config.json")
         if os.path.exists(gen):
             with open(gen) as f:

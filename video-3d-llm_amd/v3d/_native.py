@@ -53,6 +53,9 @@ SIGNATURES = {
     "v3d_gemm": (c_i, [c_p, c_l, c_p, c_l, c_p, c_p, c_l, c_i, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_p]),
     "v3d_quantize_fp8_rows": (c_i, [c_p, c_l, c_l, c_i, c_i, c_p, c_l, c_p, c_p]),
     "v3d_gemm_fp8": (c_i, [c_p, c_l, c_p, c_p, c_l, c_p, c_p, c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "v3d_quantize_mxfp4_rows": (c_i, [c_p, c_l, c_l, c_i, c_i, c_p, c_l, c_p, c_l, c_p]),
+    "v3d_gemm_mxfp4": (c_i, [c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "v3d_linear_decode_mxfp4_rows": (c_i, [c_p, c_l, c_i, c_p, c_l, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_i, c_p]),
     "v3d_rmsnorm": (c_i, [c_p, c_l, c_p, c_p, c_l, c_l, c_i, c_f, c_i, c_p]),
     "v3d_layernorm": (c_i, [c_p, c_l, c_p, c_p, c_p, c_l, c_l, c_i, c_f, c_i, c_p]),
     "v3d_rope_table_build": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p]),

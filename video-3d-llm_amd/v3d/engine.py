@@ -140,11 +140,23 @@ class SceneContext:
 class Engine:
     VIT_DP = 96      # the attention kernel's tile width for SigLIP's head dim 72
 
-    def __init__(self, cfg: EngineConfig, state_dict, dtype=torch.bfloat16, device="cuda", max_frames=32, llm_fp8=False):
+    def __init__(self, cfg: EngineConfig, state_dict, dtype=torch.bfloat16, device="cuda", max_frames=32, llm_fp8=False, llm_fp4=False):
         """llm_fp8 (BASELINE configs[3]): the decoder linears and the LM head use OCP e4m3 weights, quantised once per
         output row; the prefill also quantises the activations per token row (W8A8, MFMA), the decode step keeps them
-        16-bit (W8A16, weight streaming).  The ViT, attention, norms and the residual stream stay in `dtype`."""
-        self.cfg, self.dtype, self.device, self.llm_fp8 = cfg, dtype, device, bool(llm_fp8)
+        16-bit (W8A16, weight streaming).  The ViT, attention, norms and the residual stream stay in `dtype`.
+        llm_fp4 (not a reference path either; exclusive with llm_fp8): the seven linears of every decoder layer (wqkv, wo, wgu,
+        wd) use OCP MXFP4 weights (e2m1 codes + one E8M0 exponent per 32 k, 4.25 bits per weight): the prefill quantises the
+        activations to e4m3 exactly as llm_fp8 does (W4A8, block-scaled MFMA), the decode step keeps them 16-bit (W4A16).  The
+        16-bit copies of those matrices are dropped after quantisation (the layers then hold 0.27 of their bf16 bytes), so every
+        path runs on the codes: prefills of up to 8 rows go through the W4A16 decode linears.  The LM head stays 16-bit: it is
+        1.09 GB of the 15 GB a step streams, and the tokens hang on it directly.
+        Row limits of the decode linears: the matrix-core form needs K % 256 == 0; with intermediate % 256 == 128 the down
+        projection runs in the VALU form, which takes 4 rows per launch - llm_fp4 then launches it once per 4 rows, llm_fp8
+        refuses decode groups of more than 4 rows for such a model (v3d_linear_decode_fp8_rows)."""
+        if llm_fp8 and llm_fp4:
+            raise V3DError("llm_fp8 and llm_fp4 are mutually exclusive")
+        self.cfg, self.dtype, self.device, self.llm_fp8, self.llm_fp4 = cfg, dtype, device, bool(llm_fp8), bool(llm_fp4)
+        self.llm_quant = self.llm_fp8 or self.llm_fp4      # quantised layer linears (the e4m3 activation scratch, 256-row QKV pad)
         v, l = cfg.vit, cfg.llm
         self.hd = l.hidden // l.heads
         if self.hd != 128:
@@ -154,8 +166,8 @@ class Engine:
             raise V3DError("the SigLIP path needs head_dim 72")
         if l.hidden % 128 or l.inter % 64:
             raise V3DError("LLM hidden must be a multiple of 128 and intermediate of 64")
-        if self.llm_fp8 and (l.hidden % 256 or l.inter % 128):
-            raise V3DError("llm_fp8 needs LLM hidden to be a multiple of 256 and intermediate of 128")
+        if self.llm_quant and (l.hidden % 256 or l.inter % 128):
+            raise V3DError("llm_fp8 / llm_fp4 need LLM hidden to be a multiple of 256 and intermediate of 128")
         sd = {k: t.to(device=device, dtype=dtype) for k, t in state_dict.items()}
         self._prep_vit(sd)
         self._prep_llm(sd)
@@ -228,7 +240,7 @@ class Engine:
                               sd[p + "self_attn.v_proj.weight"]], 0)
             bqkv = torch.cat([sd[p + "self_attn.q_proj.bias"], sd[p + "self_attn.k_proj.bias"],
                               sd[p + "self_attn.v_proj.bias"]], 0)
-            nq = _up(wqkv.shape[0], 256 if self.llm_fp8 else 128)
+            nq = _up(wqkv.shape[0], 256 if self.llm_quant else 128)
             self.l_layers.append(dict(
                 ln1=sd[p + "input_layernorm.weight"].contiguous(), ln2=sd[p + "post_attention_layernorm.weight"].contiguous(),
                 wqkv=_pad2(wqkv, nq, l.hidden), bqkv=_pad1(bqkv, nq),
@@ -239,7 +251,11 @@ class Engine:
                 L = self.l_layers[-1]
                 for k in ("wqkv", "wo", "wgu", "wd"):
                     L[k + "8"] = ops.quantize_fp8_rows(L[k])
-        self.l_nqkv = self.l_layers[0]["wqkv"].shape[0] if self.l_layers else 0
+            if self.llm_fp4:
+                L = self.l_layers[-1]
+                for k in ("wqkv", "wo", "wgu", "wd"):
+                    L[k + "4"] = ops.quantize_mxfp4_rows(L.pop(k))        # the 16-bit copy is dropped: nothing reads it again
+        self.l_nqkv = self.l_layers[0]["bqkv"].shape[0] if self.l_layers else 0
         self.l_norm = sd["model.norm.weight"].contiguous()
         self.l_head = _pad2(sd["lm_head.weight"], _up(l.vocab, 128), l.hidden)
         if self.llm_fp8:
@@ -282,7 +298,7 @@ class Engine:
         w.l_h = z(S, l.hidden)
         w.l_qkv, w.l_att, w.l_act = z(S, self.l_nqkv), z(S, l.hidden), z(S, l.inter)
         w.l_q8 = w.l_s8 = None
-        if self.llm_fp8:                               # e4m3 image + row scales of the current GEMM's activations
+        if self.llm_quant:                             # e4m3 image + row scales of the current GEMM's activations
             w.l_q8 = torch.zeros((S, max(l.hidden, l.inter)), dtype=torch.uint8, device=dev)
             w.l_s8 = torch.zeros(S, dtype=torch.float32, device=dev)
         return w
@@ -444,21 +460,35 @@ class Engine:
         h, qkv, att, act = self.l_h[:S], self.l_qkv[:S], self.l_att[:S], self.l_act[:S]
         kvw = nkv * hd
         scale = 1.0 / math.sqrt(hd)
-        fp8 = self.llm_fp8 and S > 8
+        fp8 = self.llm_quant and S > 8
         if fp8:
             s8 = self.l_s8[:S]
+            if self.llm_fp4:                         # MXFP4 weights against the same e4m3 activation rows (W4A8)
+                def qgemm(q8, L, key, out, **kw):
+                    return ops.gemm_mxfp4(q8, s8, *L[key + "4"], self.dtype, out=out, **kw)
+            else:
+                def qgemm(q8, L, key, out, **kw):
+                    qw, sw = L[key + "8"]
+                    return ops.gemm_fp8(q8, s8, qw, sw, self.dtype, out=out, **kw)
 
-            def lin(a, L, key, out, **kw):           # quantise the activation rows, then the e4m3 GEMM
+            def lin(a, L, key, out, **kw):           # quantise the activation rows, then the e4m3 / MXFP4 GEMM
                 q8 = self.l_q8[:S, : a.shape[1]]
                 ops.quantize_fp8_rows(a, q8, s8)
-                qw, sw = L[key + "8"]
-                return ops.gemm_fp8(q8, s8, qw, sw, self.dtype, out=out, **kw)
+                return qgemm(q8, L, key, out, **kw)
 
             def norm_lin(ln, L, key, out, **kw):     # RMSNorm + quantisation in one pass (the 16-bit rows are never stored)
                 q8 = self.l_q8[:S, : l.hidden]
                 ops.rmsnorm_quantize_fp8(x, ln, l.eps, q8, s8)
-                qw, sw = L[key + "8"]
-                return ops.gemm_fp8(q8, s8, qw, sw, self.dtype, out=out, **kw)
+                return qgemm(q8, L, key, out, **kw)
+        elif self.llm_fp4:                           # up to 8 rows: no 16-bit weights to fall back on - the W4A16 decode linears
+            dec_epi = {ops.EPI_BIAS: ops.DEC_BIAS, ops.EPI_RES: ops.DEC_RES, ops.EPI_SWIGLU: ops.DEC_SWIGLU}
+
+            def lin(a, L, key, out, epilogue=ops.EPI_NONE, **kw):
+                return self._dec_q(a, L, key, out, epilogue=dec_epi.get(epilogue, ops.DEC_NONE), **kw)
+
+            def norm_lin(ln, L, key, out, **kw):
+                ops.rmsnorm(x, ln, l.eps, out=h)
+                return lin(h, L, key, out, **kw)
         else:
             def lin(a, L, key, out, **kw):
                 return ops.gemm(a, L[key], out=out, **kw)
@@ -503,12 +533,12 @@ class Engine:
             else:
                 attn()
             lin(att, L, "wo", x, res=x, epilogue=ops.EPI_RES)
-            if stamps is not None and i == 1 and not fp8:      # bench: HIP events around the gate/up GEMM alone
+            if stamps is not None and i == 1 and not fp8 and "wgu" in L:      # bench: HIP events around the gate/up GEMM alone
                 ops.rmsnorm(x, L["ln2"], l.eps, out=h)
                 stamps["gemm"](lambda: ops.gemm(h, L["wgu"], epilogue=ops.EPI_SWIGLU, out=act))
-            elif stamps is not None and i == 1:                # e4m3: norm + quantisation pass, then the stamped GEMM
+            elif stamps is not None and i == 1 and fp8:        # e4m3 / MXFP4: norm + quantisation pass, then the stamped GEMM
                 ops.rmsnorm_quantize_fp8(x, L["ln2"], l.eps, self.l_q8[:S, : l.hidden], s8)
-                stamps["gemm"](lambda: ops.gemm_fp8(self.l_q8[:S, : l.hidden], s8, *L["wgu8"], self.dtype, epilogue=ops.EPI_SWIGLU, out=act))
+                stamps["gemm"](lambda: qgemm(self.l_q8[:S, : l.hidden], L, "wgu", act, epilogue=ops.EPI_SWIGLU))
             else:
                 norm_lin(L["ln2"], L, "wgu", act, epilogue=ops.EPI_SWIGLU)
             lin(act, L, "wd", x, res=x, epilogue=ops.EPI_RES)
@@ -529,16 +559,29 @@ class Engine:
         for r in rows:
             xr = x[r]
             ops.attention_decode(qkv[r], cache, cache[:, kvw:], att, pos0 + r + 1, nh, nkv, scale, self.dec_ws)
-            if self.llm_fp8:
+            if self.llm_quant:
                 row = x[r: r + 1]
-                ops.linear_decode_fp8_rows(att[None], *L["wo8"], row, res=row, epilogue=ops.DEC_RES)
+                self._dec_q(att[None], L, "wo", row, res=row, epilogue=ops.DEC_RES)
                 h1 = ops.rmsnorm(row, L["ln2"], l.eps, out=self.l_h[:1])
-                ops.linear_decode_fp8_rows(h1, *L["wgu8"], act[None], epilogue=ops.DEC_SWIGLU)
-                ops.linear_decode_fp8_rows(act[None], *L["wd8"], row, res=row, epilogue=ops.DEC_RES)
+                self._dec_q(h1, L, "wgu", act[None], epilogue=ops.DEC_SWIGLU)
+                self._dec_q(act[None], L, "wd", row, res=row, epilogue=ops.DEC_RES)
             else:
                 ops.linear_decode(att, L["wo"], xr, res=xr, epilogue=ops.DEC_RES)
                 ops.linear_decode(xr, L["wgu"], act, norm_weight=L["ln2"], eps=l.eps, epilogue=ops.DEC_SWIGLU)
                 ops.linear_decode(act, L["wd"], xr, res=xr, epilogue=ops.DEC_RES)
+
+    def _dec_q(self, a, L, key, out, **kw):
+        """decode linear of rows a over the quantised image of L[key]: e4m3 (llm_fp8, W8A16) or MXFP4 (llm_fp4, W4A16)"""
+        if self.llm_fp4:
+            q, e = L[key + "4"]
+            M = a.shape[0]
+            if M <= 4 or q.shape[1] % 128 == 0:      # K % 256 == 0: one launch (matrix-core form for 2..32 rows)
+                return ops.linear_decode_mxfp4_rows(a, q, e, out, **kw)
+            res = kw.pop("res", None)                # VALU form: 4 rows per launch; a row's bits do not depend on its group
+            for m in range(0, M, 4):
+                ops.linear_decode_mxfp4_rows(a[m: m + 4], q, e, out[m: m + 4], res=None if res is None else res[m: m + 4], **kw)
+            return out
+        return ops.linear_decode_fp8_rows(a, *L[key + "8"], out, **kw)
 
     def _head(self, x_row):
         """final RMSNorm + LM head on ONE row (K18: only the last position feeds generation)."""
@@ -554,7 +597,7 @@ class Engine:
         """One new token (x_row [1, hidden], in place) at position `pos`: 7 launches per layer, no host sync.
         RMSNorms are fused into the QKV / gate-up linears, rotary + cache append into one kernel."""
         l = self.cfg.llm
-        if self.llm_fp8:                  # e4m3 weights: the row goes through the (unfused-norm) rows path as a group of one
+        if self.llm_quant:                # e4m3 / MXFP4 weights: the row goes through the (unfused-norm) rows path as a group of one
             g = getattr(self.ctx, "g1", None)
             if g is None:
                 g = self.ctx.g1 = self.new_group(1)
@@ -865,16 +908,16 @@ class Engine:
         scale = 1.0 / math.sqrt(hd)
         x, h, qkv, att, act = g.x[:M], g.h[:M], g.qkv[:M], g.att[:M], g.act[:M]
         sk = [p + 1 for p in positions]
-        if self.llm_fp8:                  # configs[3]: e4m3 weights, 16-bit activations (W8A16) - half the bytes per step
+        if self.llm_quant:                # e4m3 (configs[3], W8A16) or MXFP4 (W4A16) weights, 16-bit activations: half / 0.27 of the bytes per step
             def lin(a, L, key, out, **kw):
-                return ops.linear_decode_fp8_rows(a, *L[key + "8"], out, **kw)
+                return self._dec_q(a, L, key, out, **kw)
         else:
             def lin(a, L, key, out, **kw):
                 return ops.linear_decode_rows(a, L[key], out, **kw)
         # r04: with more than four rows the persistent decode linear forms the RMSNorm of its input rows itself (the bits of rmsnorm() +
         # the unfused call: ops.linear_decode_rows_fuses_norm) - two launches fewer per layer and one before the LM head
-        def norm_lin(a, nw, w, out, **kw):
-            if not self.llm_fp8 and ops.linear_decode_rows_fuses_norm(M, w.shape[0], w.shape[1], kw.get("epilogue", ops.DEC_NONE)):
+        def norm_lin(a, nw, w, out, quant=self.llm_quant, **kw):
+            if not quant and ops.linear_decode_rows_fuses_norm(M, w.shape[0], w.shape[1], kw.get("epilogue", ops.DEC_NONE)):
                 return ops.linear_decode_rows(a, w, out, norm_weight=nw, eps=l.eps, **kw)
             return None
         for i, L in enumerate(self.l_layers):
@@ -895,7 +938,7 @@ class Engine:
         if self.llm_fp8:
             ops.rmsnorm(x, self.l_norm, l.eps, out=g.last[:M])
             ops.linear_decode_fp8_rows(g.last[:M], *self.l_head8, g.logits[:M])
-        elif norm_lin(x, self.l_norm, self.l_head, g.logits[:M]) is None:
+        elif norm_lin(x, self.l_norm, self.l_head, g.logits[:M], quant=False) is None:     # (llm_fp4 keeps the 16-bit head)
             ops.rmsnorm(x, self.l_norm, l.eps, out=g.last[:M])
             ops.linear_decode_rows(g.last[:M], self.l_head, g.logits[:M])
         return g.logits[:M, : l.vocab]

@@ -336,9 +336,16 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
     return pipelined if pipeline else one_by_one
 
 
-def load_model(model_path, overwrite_cfg=False):
+LLM_WEIGHTS = ("bf16", "fp8", "fp4")
+
+
+def load_model(model_path, overwrite_cfg=False, llm_weights="bf16"):
     """load_pretrained_model (llava/model/builder.py) - the reference's own loader when its checkout is importable behind the
-    overlay, else the same call sequence from v3d.loader."""
+    overlay, else the same call sequence from v3d.loader.  llm_weights "fp8" / "fp4" (e4m3 / MXFP4
+    decoder linears, Engine(llm_fp8=) / Engine(llm_fp4=); not reference paths) always load through v3d.loader: the reference's
+    loader has no such switch."""
+    if llm_weights not in LLM_WEIGHTS:
+        raise ValueError(f"llm_weights {llm_weights!r}: one of {LLM_WEIGHTS}")
     from llava.mm_utils import get_model_name_from_path
     name = get_model_name_from_path(model_path)
     overwrite = {"tie_word_embeddings": False, "use_cache": True, "vocab_size": 151649} if overwrite_cfg else {}     # model_scanqa.py:94-99
@@ -346,6 +353,10 @@ def load_model(model_path, overwrite_cfg=False):
         from llava.model.builder import load_pretrained_model
     except ImportError:
         from .loader import load_pretrained_model
+    if llm_weights != "bf16":
+        from .loader import load_pretrained_model as load_quantised
+        tokenizer, model, image_processor, _ = load_quantised(model_path, None, name, overwrite_config=overwrite, llm_weights=llm_weights)
+        return tokenizer, model, image_processor, name
     tokenizer, model, image_processor, _ = load_pretrained_model(model_path, None, name, overwrite_config=overwrite)
     return tokenizer, model, image_processor, name
 
@@ -370,6 +381,8 @@ def main(argv=None):
                     help="host processes decoding frames ahead of the GPU (0: cores / ranks, at most 16; -1: none, decode on the main thread)")
     ap.add_argument("--shard", choices=("stride", "scene"), default=None,
                     help="stride: questions[rank::world] (the reference); scene: whole scenes per rank (default with --reuse-scenes)")
+    ap.add_argument("--llm-weights", choices=LLM_WEIGHTS, default="bf16",
+                    help="decoder linears: 16-bit as the checkpoint stores them (default), OCP e4m3 (fp8) or OCP MXFP4 (fp4); the last two are not reference paths")
     ap.add_argument("--n_gpu", type=int, default=None,
                     help="the reference's flag (model_scanqa.py:222): started plainly with N > 1, launch N ranks of this runner on this node")
     a = ap.parse_args(argv)
@@ -387,7 +400,7 @@ def main(argv=None):
         pool = frame_io.make_pool(a.loader_workers or default_workers())        # forked before this process touches the GPU
     rank, world, dev, gather_dev = rank_setup(a.n_gpu)
     from llava.video_utils import VideoProcessor
-    tokenizer, model, image_processor, name = load_model(os.path.expanduser(a.model_path), a.overwrite_cfg)
+    tokenizer, model, image_processor, name = load_model(os.path.expanduser(a.model_path), a.overwrite_cfg, a.llm_weights)
     vp = VideoProcessor(video_folder=a.video_folder, annotation_dir=a.embodiedscan_folder, frame_sampling_strategy=a.frame_sampling_strategy,
                         metadata_dir=a.metadata_folder)
     times = []

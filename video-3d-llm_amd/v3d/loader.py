@@ -103,10 +103,11 @@ def drop_deleted_tower_layer(sd, tower_from_raw_siglip):
 
 
 def load_pretrained_model(model_path, model_base=None, model_name=None, device_map="auto", torch_dtype="float16",
-                          attn_implementation="flash_attention_2", overwrite_config=None, **kwargs):
+                          attn_implementation="flash_attention_2", overwrite_config=None, llm_weights="bf16", **kwargs):
     """The LLaVA-Qwen branch of llava.model.builder.load_pretrained_model (builder.py:26-36, 206-228, 266-292) for callers that
     run without the reference checkout on the path: tokenizer, LlavaQwenForCausalLM.from_pretrained with the same keyword
-    arguments, resize_token_embeddings, the tower's image processor, the context length.  Same return tuple."""
+    arguments, resize_token_embeddings, the tower's image processor, the context length.  Same return tuple.  llm_weights "fp8" / "fp4":
+    e4m3 / MXFP4 decoder linears (Engine(llm_fp8=) / Engine(llm_fp4=)); the reference has neither."""
     from transformers import AutoTokenizer
 
     from llava.model import LlavaQwenConfig, LlavaQwenForCausalLM
@@ -120,7 +121,8 @@ def load_pretrained_model(model_path, model_base=None, model_name=None, device_m
         for k, v in overwrite_config.items():
             setattr(cfg, k, v)
     model = LlavaQwenForCausalLM.from_pretrained(model_path, low_cpu_mem_usage=True, attn_implementation=attn_implementation, config=cfg,
-                                                 device_map=device_map, torch_dtype=dt)
+                                                 device_map=device_map, torch_dtype=dt, llm_fp8=llm_weights == "fp8",
+                                                 llm_fp4=llm_weights == "fp4")
     # builder.py:266-275: the image patch / start / end tokens join the tokenizer before the tables are resized to len(tokenizer)
     # (mm_use_im_patch_token defaults to True upstream) - mirrored so that both loaders see the same vocabulary size
     if getattr(model.config, "mm_use_im_patch_token", True):

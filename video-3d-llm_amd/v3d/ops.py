@@ -373,6 +373,58 @@ def gemm_fp8(qa, sa, qw, sw, out_dtype, bias=None, res=None, epilogue=EPI_NONE, 
     return out
 
 
+# ------------------------------------------------------------------------------ MXFP4 weights (not a reference path)
+
+
+def quantize_mxfp4_rows(w):
+    """w [N, K] f16/bf16 (finite, K % 128 == 0) -> (q uint8 [N, K/2], e uint8 [N, K/32]): OCP MXFP4, two e2m1 codes per byte
+    (even k in the low nibble) and one E8M0 exponent per 32 k (v3d.h).  Non-finite weights are refused here."""
+    if w.dim() != 2 or w.dtype not in (torch.float16, torch.bfloat16):
+        raise V3DError("quantize_mxfp4_rows: w must be a 2-D f16/bf16 tensor")
+    if not bool(torch.isfinite(w).all()):
+        raise V3DError("quantize_mxfp4_rows: non-finite weights are outside the MXFP4 contract")
+    rows, cols = w.shape
+    if w.stride(1) != 1:
+        w = w.contiguous()
+    q = torch.empty((rows, cols // 2), dtype=torch.uint8, device=w.device)
+    e = torch.empty((rows, cols // 32), dtype=torch.uint8, device=w.device)
+    check(lib().v3d_quantize_mxfp4_rows(_p(w), w.stride(0), rows, cols, _code(w), _p(q), q.stride(0), _p(e), e.stride(0), _stream()),
+          "v3d_quantize_mxfp4_rows")
+    return q, e
+
+
+def _check_mxfp4(what, q, e, K, **others):
+    """(q [N, K/2], e [N, K/32]) are uint8 matrices with unit inner stride on one device, the other operands too"""
+    for name, t, dt in [("q", q, torch.uint8), ("e", e, torch.uint8)] + [(n, t, d) for n, (t, d) in others.items()]:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != q.device:
+            raise V3DError(f"{what}: {name} must be a CUDA/HIP tensor on the device of q")
+        if dt is not None and t.dtype != dt:
+            raise V3DError(f"{what}: {name} is {t.dtype}, expected {dt}")
+        if t.dim() == 2 and t.stride(1) != 1 or t.dim() == 1 and t.numel() > 1 and t.stride(0) != 1:
+            raise V3DError(f"{what}: {name} must have unit inner stride (got strides {tuple(t.stride())})")
+    if q.dim() != 2 or e.dim() != 2 or q.shape[1] * 2 != K or e.shape != (q.shape[0], K // 32):
+        raise V3DError(f"{what}: q {tuple(q.shape)} / e {tuple(e.shape)} do not match K={K}")
+
+
+def gemm_mxfp4(qa, sa, q, e, out_dtype, bias=None, res=None, epilogue=EPI_NONE, out=None):
+    """out = epilogue( (qa @ deq(q, e).T) * sa[:,None] ); qa [M,K] e4m3 bytes + sa [M] as quantize_fp8_rows writes them,
+    (q [N,K/2], e [N,K/32]) as quantize_mxfp4_rows writes them (W4A8 prefill)."""
+    if not isinstance(qa, torch.Tensor) or qa.dim() != 2:
+        raise V3DError("gemm_mxfp4: qa must be a 2-D uint8 tensor")
+    M, K = qa.shape
+    _check_mxfp4("gemm_mxfp4", q, e, K, qa=(qa, torch.uint8), sa=(sa, torch.float32))
+    if sa.shape != (M,):
+        raise V3DError(f"gemm_mxfp4: sa {tuple(sa.shape)} does not match M={M}")
+    N = q.shape[0]
+    n_out = N // 2 if epilogue == EPI_SWIGLU else N
+    if out is None:
+        out = torch.empty((M, n_out), dtype=out_dtype, device=qa.device)
+    check(lib().v3d_gemm_mxfp4(_p(qa), qa.stride(0), _p(sa), _p(q), q.stride(0), _p(e), e.stride(0), _p(bias), _p(res),
+                               res.stride(0) if res is not None else 0, _p(out), out.stride(0), M, N, K, _DT[out_dtype],
+                               epilogue, _stream()), "v3d_gemm_mxfp4")
+    return out
+
+
 # ------------------------------------------------------------------------------ norms / rotary
 
 
@@ -534,6 +586,19 @@ def linear_decode_fp8_rows(x, qw, sw, out, bias=None, res=None, epilogue=DEC_NON
     check(lib().v3d_linear_decode_fp8_rows(_p(x), x.stride(0), M, _p(qw), qw.stride(0), _p(sw), _p(bias), _p(res),
                                            res.stride(0) if res is not None else 0, _p(out), out.stride(0), N, K, _code(x),
                                            epilogue, _stream()), "v3d_linear_decode_fp8_rows")
+    return out
+
+
+def linear_decode_mxfp4_rows(x, q, e, out, bias=None, res=None, epilogue=DEC_NONE):
+    """x [M, K] 16-bit rows against MXFP4 weights (q [N, K/2], e [N, K/32]) as quantize_mxfp4_rows writes them (W4A16 decode)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype not in (torch.float16, torch.bfloat16):
+        raise V3DError("linear_decode_mxfp4_rows: x must be a 2-D f16/bf16 tensor")
+    M, K = x.shape
+    _check_mxfp4("linear_decode_mxfp4_rows", q, e, K, x=(x, None), out=(out, x.dtype))
+    N = q.shape[0]
+    check(lib().v3d_linear_decode_mxfp4_rows(_p(x), x.stride(0), M, _p(q), q.stride(0), _p(e), e.stride(0), _p(bias), _p(res),
+                                             res.stride(0) if res is not None else 0, _p(out), out.stride(0), N, K, _code(x),
+                                             epilogue, _stream()), "v3d_linear_decode_mxfp4_rows")
     return out
 
 
