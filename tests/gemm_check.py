@@ -108,9 +108,11 @@ def n_out(N, epi):
     return N // 2 if epi == EPI_SWIGLU else N
 
 
-def reference(a, w, bias=None, res=None, epi=EPI_NONE, res_mod=0, rows=None):
+def reference(a, w, bias=None, res=None, epi=EPI_NONE, res_mod=0, rows=None, lin_rel=0.0):
     """The rows `rows` (a slice, default all) of epilogue(a w^T) -> dict of f64 [R, n_out]: out, bound, rounded, and for the GELUs and
-    SwiGLU lo / hi (the interval a kernel must hit when yr is exact).  ymax = max |y| (linear output) of these rows."""
+    SwiGLU lo / hi (the interval a kernel must hit when yr is exact).  ymax = max |y| (linear output) of these rows.
+    lin_rel (0 for v3d_gemm): a further relative f32 rounding of the linear output, lin += lin_rel |y| (tests/decode_check.py: the e4m3
+    decode rows multiply the f32 sum by the row scale once, 2^-24 |y|); w may be given in f64 (dequantised weights)."""
     dt = a.dtype
     h = H[dt]
     tiny = TINY if dt == torch.float16 else 0.0
@@ -124,7 +126,7 @@ def reference(a, w, bias=None, res=None, epi=EPI_NONE, res_mod=0, rows=None):
     if epi in HAS_BIAS:
         y = y + bias.double()
         mag = mag + bias.double().abs()
-    lin = C_ACC * (K / 32.0 + C0) * 2.0 ** -24 * mag + h * y.abs() + tiny
+    lin = C_ACC * (K / 32.0 + C0) * 2.0 ** -24 * mag + (h + lin_rel) * y.abs() + tiny
     del mag
     ymax = y.abs().max().item()
     if dt == torch.float16:
@@ -163,7 +165,7 @@ def reference(a, w, bias=None, res=None, epi=EPI_NONE, res_mod=0, rows=None):
     return o
 
 
-def compare(got, a, w, bias=None, res=None, epi=EPI_NONE, res_mod=0, exact=False, block=2048):
+def compare(got, a, w, bias=None, res=None, epi=EPI_NONE, res_mod=0, exact=False, block=2048, lin_rel=0.0):
     """Every element of got [M, n_out] against the reference, in row blocks -> dict:
     ratio     worst |got - out| / bound (inf if any element is not finite: never written, or NaN)
     unequal   elements that differ from `rounded`;  outside: elements outside [lo, hi] (GELUs, SwiGLU; = unequal for the others)
@@ -174,7 +176,7 @@ def compare(got, a, w, bias=None, res=None, epi=EPI_NONE, res_mod=0, exact=False
     worst, unequal, outside, ymax, need = 0.0, 0, 0, 0.0, 0
     for r0 in range(0, M, block):
         rows = slice(r0, min(M, r0 + block))
-        ref = reference(a, w, bias, res, epi, res_mod, rows)
+        ref = reference(a, w, bias, res, epi, res_mod, rows, lin_rel)
         g = got[rows].to(ref["out"].device).double()
         if not bool(torch.isfinite(g).all()):
             worst = float("inf")
