@@ -167,6 +167,22 @@ enum {
 int v3d_gemm(const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, const void* res,
              int64_t ldr, int res_mod, void* out, int64_t ldo, int M, int N, int K, int dtype, int epilogue,
              void* stream);
+/* The same product with a layout flag per operand: out[M, N] = epilogue(op(A) . op(B)).
+ *   kmajor = 0   element (row r, k) at ptr[r * ld + k] (K-contiguous: v3d_gemm's layout), ld >= K;
+ *   kmajor = 1   element (row r, k) at ptr[k * ld + r]: the stored matrix is [K, rows], contiguous along the output dimension,
+ *                ld >= rows (M for A, N for B).
+ * (0, 1) is dx = dy . W on an nn.Linear weight as stored, (1, 1) dW = dy^T . x on dy and x as stored - the two products of a
+ * linear's backward without a transposed copy (v3d/train.py: linear_backward under V3D_TRAIN_GEMM_LAYOUTS=1).  (0, 0) IS v3d_gemm
+ * (forwarded unchanged).  With a k-major operand: 16-bit MFMA tile kernels only (128 x 128 x 64, or 256 x 256 x 64 where N % 256 == 0
+ * and the cost model prefers it; V3D_GEMM_LAYOUT_TILE=128 / 256 forces one, read per call), no skinny path, no split-K tail;
+ * epilogues NONE and RES only (`bias` is not read), every other one is refused with V3D_E_INVALID;
+ * N % 128 == 0; every ld a multiple of 8; pointers 16-byte aligned; a k-major A needs M % 8 == 0;
+ * K % 64 == 0 unless BOTH operands are k-major - then K is a row count and any K >= 1 is taken (the k-rows past K of the last
+ * K-step are read from a zero-filled line, never from the operands); an operand spans fewer than 2^31 elements.
+ * Summation order: k ascending in one run per output; rounding points as v3d_gemm.  All checks run before any device call. */
+int v3d_gemm_layout(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb, int b_kmajor,
+                    const void* bias, const void* res, int64_t ldr, int res_mod, void* out, int64_t ldo,
+                    int M, int N, int K, int dtype, int epilogue, void* stream);
 
 /* FP8 (OCP e4m3) variant of the LLM linears - BASELINE configs[3]; not part of the reference (tolerance is
  * re-stated in tests/test_gpu_fp8.py).  y[m,n] = sa[m] * sw[n] * sum_k qa[m,k] qw[n,k] with per-row scales.

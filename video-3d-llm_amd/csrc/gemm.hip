@@ -21,6 +21,7 @@
 #include "v3d_common.h"
 #include <mutex>
 #include <unordered_map>
+#include <utility>
 
 namespace v3d {
 
@@ -1416,6 +1417,305 @@ static int launch_gemv(const GemmArgs& p, int epi, hipStream_t st) {
   return check_launch("v3d_gemm (skinny)");
 }
 
+// ------------------------------------------------------------------------------------------
+// Operand layouts (v3d_gemm_layout): out[M, N] = epilogue(op(A) . op(B)), each operand either K-contiguous (element (row r, k) at
+// ptr[r ld + k], the layout of every kernel above) or K-MAJOR (ptr[k ld + r]: the stored matrix is [K, rows]).  NN (A K-contiguous,
+// B k-major) is dx = dy . W on W as stored, TN (both k-major) dW = dy^T . x on dy and x as stored.
+//
+// One kernel body in two tile forms, BIG = false: 128 x 128 x 64, 4 waves (2 x 2) of 64 x 64, two workgroups per CU;
+// BIG = true: 256 x 256 x 64, 8 waves (2 x 4) of 128 x 64, one workgroup per CU - the geometry, the 2-deep LDS-DMA ring and the
+// four-phase K-step of gemm256x256_kernel (the fragment reads of phase p+1 in flight under the MFMAs of phase p, one barrier per K-step).
+// An operand tile is 1 or 2 PANELS of 16 KiB:
+//   K-contiguous  [128 rows][64 k], 128-byte rows, the swizzle of the kernels above; fragments by ds_read_b128;
+//   k-major       [64 k][128 rows], 256-byte rows, 16-byte chunk ch of k-row r at 256 r + 16 (ch ^ (((r & 3) << 2) | ((r >> 2) & 3)));
+//                 a 16 x 32 fragment is two ds_read_b64_tr_b16 (k-rows 8g .. 8g+3 and 8g+4 .. 8g+7 for lane group g = lane >> 4:
+//                 element j of a lane is k = 8g + j, the order of the row read, so the two kinds of operand can be mixed), lane 4q+p
+//                 of a group at off(r0 + q, c0 + (p >> 1)) + 8 (p & 1).  In one instruction the two groups of a 32-lane half read
+//                 blocks 8 k-rows apart, and the XOR spreads the 32 lanes over all 64 banks: conflict-free.
+// A DMA piece is 1 KiB either way (8 rows of 128 bytes or 4 k-rows of 256 bytes), 4 pieces per wave and operand.
+// Tails never mask a lane (the transposed read needs EXEC all ones, and a DMA lane that does not write would leave stale LDS):
+//   M     K-contiguous A: rows >= M re-read row M - 1;  k-major A: 8-column chunks at or beyond M re-read the last whole chunk (M % 8 == 0);
+//         neither is stored;
+//   K     both operands k-major: K is a row count, any K >= 1; in the last, partial K-step the lanes of k-rows >= K read a zero-filled
+//         device line, for BOTH operands (0 . x could be NaN).  Otherwise K % 64 == 0.
+// ------------------------------------------------------------------------------------------
+constexpr int LP_BYTES = 128 * BK * 2;                  // one panel, 16 KiB
+__device__ __attribute__((aligned(256))) unsigned char g_gemm_zero_line[256];     // zero-initialised with the module
+
+using lp_v4i = __attribute__((ext_vector_type(4))) int;
+using lp_v2i = __attribute__((ext_vector_type(2))) int;
+template <bool KM> struct LpFrag;
+template <> struct LpFrag<false> { lp_v4i v; };
+template <> struct LpFrag<true> { lp_v2i lo, hi; };
+__device__ __forceinline__ lp_v4i lp_get(const LpFrag<false>& f) { return f.v; }
+__device__ __forceinline__ lp_v4i lp_get(const LpFrag<true>& f) { return lp_v4i{f.lo[0], f.lo[1], f.hi[0], f.hi[1]}; }
+// a wait retires registers only through the pins behind it: volatile asm statements keep their order, and every consumer of a
+// fragment depends on its pin ("+v"), so none can be scheduled above the s_waitcnt (cdna guide 5.7, form ii)
+__device__ __forceinline__ void lp_pin(LpFrag<false>& f) { asm volatile("" : "+v"(f.v)); }
+__device__ __forceinline__ void lp_pin(LpFrag<true>& f) { asm volatile("" : "+v"(f.lo), "+v"(f.hi)); }
+template <int N, bool KM> __device__ __forceinline__ void lp_pin_all(LpFrag<KM> (&f)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) lp_pin(f[i]);
+}
+template <int CNT> __device__ __forceinline__ void lp_wait() {      // (the counter has 4 bits: a count above 15 waits for one read more)
+  asm volatile("s_waitcnt lgkmcnt(%0)" : : "n"(CNT < 15 ? CNT : 15) : "memory");
+}
+// per-lane read addresses of one operand inside a stage.  Row image: r0 / r1 = the k-half 0 / 1 address of fragment 0.
+// k-major image: r0 = panel + 256 (8g + q) + 8 (p & 1), r1 = 16 * (chunk ^ XOR) of fragment 0's first block (k-rows 8g ..).
+struct LpAddr { unsigned r0, r1; };
+// fragment F of the wave, k-half KS: row image at + 2048 F; k-major image 16 columns on = chunk + 2 F, second block = 4 k-rows on
+template <int KS, int F> __device__ __forceinline__ void lp_read(LpFrag<false>& f, unsigned tile, LpAddr ad) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f.v) : "v"(tile + (KS ? ad.r1 : ad.r0)), "n"(F * 2048));
+}
+template <int KS, int F> __device__ __forceinline__ void lp_read(LpFrag<true>& f, unsigned tile, LpAddr ad) {
+  const unsigned a0 = tile + ad.r0 + (ad.r1 ^ (unsigned)(32 * F)), a1 = tile + ad.r0 + (ad.r1 ^ (unsigned)(32 * F + 16));
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.lo) : "v"(a0), "n"(KS * 8192));
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.hi) : "v"(a1), "n"(KS * 8192 + 1024));
+}
+template <int KS, int FIRST, bool KM, int... I>
+__device__ __forceinline__ void lp_read_set(LpFrag<KM>* f, unsigned tile, LpAddr ad, std::integer_sequence<int, I...>) {
+  (lp_read<KS, FIRST + I>(f[I], tile, ad), ...);
+}
+
+template <typename T, int EPI, bool AKM, bool BKM, bool BIG>
+__global__ __launch_bounds__(BIG ? 512 : 256, 2) void gemm_layout_kernel(GemmArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  using M16 = Mfma16<T>;
+  using frag = typename M16::frag;
+  constexpr int NP = BIG ? 2 : 1;                   // panels per operand tile
+  constexpr int NWN = BIG ? 4 : 2;                  // waves along n
+  constexpr int MT = BIG ? 8 : 4, MG = MT / 2;      // 16-row accumulator tiles per wave along m, per phase
+  constexpr int WROWS = MT * 16, LBM = 2 * WROWS, LBN = NP * 128;
+  constexpr int TILE = NP * LP_BYTES, STAGE = 2 * TILE;
+  constexpr int RA = AKM ? 2 : 1, RB = BKM ? 2 : 1; // LDS reads per fragment
+  constexpr bool KTAIL = AKM && BKM;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave / NWN, wn = wave % NWN;
+  const int pw = wave >> 2, w4 = wave & 3;          // staging: wave moves pieces 4 w4 .. 4 w4 + 3 of panel pw of both operands
+  int tm, tn;
+  tile_of_block(blockIdx.x, gridDim.x, p.tiles_m, p.tiles_n, tm, tn);
+  const int m0 = tm * LBM, n0 = tn * LBN;
+
+  // ---- staging: per-lane source BYTE offsets (below 2^32: the host checks the operands' sizes); the K-step advances the base ----
+  unsigned a_off[4], b_off[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if constexpr (AKM) {
+      const int krow = w4 * 16 + 4 * i + (lane >> 4);                         // (krow & 3) = lane >> 4, ((krow >> 2) & 3) = i
+      const int ch = (lane & 15) ^ (((lane >> 4) << 2) | i);
+      int gm = m0 + pw * 128 + ch * 8;
+      gm = gm <= p.M - 8 ? gm : p.M - 8;                                      // M tail: the last whole chunk, never stored
+      a_off[i] = (unsigned)(krow * (int)p.lda + gm) * 2u;
+    } else {
+      const int row = pw * 128 + w4 * 32 + i * 8 + (lane >> 3);
+      const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+      int gm = m0 + row;
+      gm = gm < p.M ? gm : p.M - 1;
+      a_off[i] = (unsigned)(gm * (int)p.lda + chunk * 8) * 2u;
+    }
+    if constexpr (BKM) {
+      const int krow = w4 * 16 + 4 * i + (lane >> 4);
+      const int ch = (lane & 15) ^ (((lane >> 4) << 2) | i);
+      b_off[i] = (unsigned)(krow * (int)p.ldw + n0 + pw * 128 + ch * 8) * 2u;
+    } else {
+      const int row = pw * 128 + w4 * 32 + i * 8 + (lane >> 3);
+      const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+      b_off[i] = (unsigned)((n0 + row) * (int)p.ldw + chunk * 8) * 2u;
+    }
+  }
+  const size_t a_step = AKM ? (size_t)p.lda * (BK * 2) : (size_t)(BK * 2), b_step = BKM ? (size_t)p.ldw * (BK * 2) : (size_t)(BK * 2);
+  auto stage = [&](int buf, int kt) {
+    char* sa = smem + buf * STAGE + pw * LP_BYTES + w4 * 4096;
+    char* sb = sa + TILE;
+    const char* Ak = (const char*)p.A + (size_t)kt * a_step;
+    const char* Bk = (const char*)p.W + (size_t)kt * b_step;
+    if (KTAIL && kt * BK + BK > p.K) {             // the partial last K-step: k-rows >= K come from the zero line
+      const char* zero = (const char*)g_gemm_zero_line + (lane & 15) * 16;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool in = kt * BK + w4 * 16 + 4 * i + (lane >> 4) < p.K;
+        glds16(in ? Ak + a_off[i] : zero, sa + i * 1024);
+        glds16(in ? Bk + b_off[i] : zero, sb + i * 1024);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        glds16(Ak + a_off[i], sa + i * 1024);
+        glds16(Bk + b_off[i], sb + i * 1024);
+      }
+    }
+  };
+
+  // ---- fragment read addresses ----
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  LpAddr adA, adB;
+  {
+    const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
+    const unsigned sw = (lane >> 1) & 7, frow = (lane & 15) * (BK * 2);      // row image: all wave row bases are multiples of 16
+    const unsigned row0 = frow + (((0 + g) ^ sw) << 4), row1 = frow + (((4 + g) ^ sw) << 4);
+    const unsigned trb = 256 * (8 * g + q) + 8 * (pp & 1);
+    const unsigned trc = 16 * ((pp >> 1) ^ ((q << 2) | (2 * (g & 1))));       // chunk 0's slot in k-row 8g + q (first block: (row >> 2) & 3 = 2 (g & 1))
+    // wave tile: m rows wm WROWS .. (panel wm, chunk 0 when BIG; panel 0, chunk 8 wm otherwise), n columns 64 wn .. (panel wn >> 1, chunk 8 (wn & 1))
+    if constexpr (AKM) { adA.r0 = (BIG ? wm * LP_BYTES : 0) + trb; adA.r1 = trc ^ (BIG ? 0u : (unsigned)(128 * wm)); }
+    else { adA.r0 = (wm * WROWS) * (BK * 2) + row0; adA.r1 = (wm * WROWS) * (BK * 2) + row1; }
+    if constexpr (BKM) { adB.r0 = (wn >> 1) * LP_BYTES + trb; adB.r1 = trc ^ (unsigned)(128 * (wn & 1)); }
+    else { adB.r0 = (wn * 64) * (BK * 2) + row0; adB.r1 = (wn * 64) * (BK * 2) + row1; }
+  }
+
+  f32x4 acc[4][MT];   // [ni][mi], transposed product: D[row = n][col = m]
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < MT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  LpFrag<AKM> A0[MG], A1[MG];
+  LpFrag<BKM> B0[4], B1[4];
+  using SeqA = std::make_integer_sequence<int, MG>;
+  using SeqB = std::make_integer_sequence<int, 4>;
+#define V3D_LMMA(FA, FB, G)                                                                            \
+  {                                                                                                    \
+    __builtin_amdgcn_s_setprio(1);                                                                     \
+    _Pragma("unroll") for (int i = 0; i < MG; ++i)                                                     \
+    _Pragma("unroll") for (int ni = 0; ni < 4; ++ni)                                                   \
+        acc[ni][(G) * MG + i] = M16::run(__builtin_bit_cast(frag, lp_get(FB[ni])), __builtin_bit_cast(frag, lp_get(FA[i])), acc[ni][(G) * MG + i]); \
+    __builtin_amdgcn_s_setprio(0);                                                                     \
+  }
+
+  const int nt = (p.K + BK - 1) / BK;
+  stage(0, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  if (nt > 1) stage(1, 1);
+  lp_read_set<0, 0>(A0, lds0, adA, SeqA{});
+  lp_read_set<0, 0>(B0, lds0 + TILE, adB, SeqB{});
+  for (int t = 0; t < nt; ++t) {
+    const unsigned ta = lds0 + (t & 1) * STAGE, tb = ta + TILE;
+    const unsigned na = lds0 + ((t & 1) ^ 1) * STAGE, nb = na + TILE;
+    asm volatile("" : "+v"(adA.r1), "+v"(adB.r1));        // keep the per-fragment address arithmetic inside the loop (hoisted, it costs 2 registers per read)
+    // phase 0: k-half 0, first group of m-tiles
+    lp_read_set<0, MG>(A1, ta, adA, SeqA{});
+    lp_wait<MG * RA>();
+    lp_pin_all(A0); lp_pin_all(B0);
+    V3D_LMMA(A0, B0, 0);
+    // phase 1: k-half 0, second group
+    lp_read_set<1, 0>(A0, ta, adA, SeqA{});
+    lp_read_set<1, 0>(B1, tb, adB, SeqB{});
+    lp_wait<MG * RA + 4 * RB>();
+    lp_pin_all(A1);
+    V3D_LMMA(A1, B0, 1);
+    // phase 2: k-half 1, first group
+    lp_read_set<1, MG>(A1, ta, adA, SeqA{});
+    lp_wait<MG * RA>();
+    lp_pin_all(A0); lp_pin_all(B1);
+    V3D_LMMA(A0, B1, 0);
+    // phase 3: k-half 1, second group; tile t fully read by this wave, its share of tile t+1 landed -> rendezvous, restage
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    lp_pin_all(A1);
+    __builtin_amdgcn_s_barrier();
+    if (t + 2 < nt) stage(t & 1, t + 2);
+    lp_read_set<0, 0>(A0, na, adA, SeqA{});               // next tile's phase-0 fragments (last step: stale, unused)
+    lp_read_set<0, 0>(B0, nb, adB, SeqB{});
+    V3D_LMMA(A1, B1, 1);
+  }
+  lp_wait<0>();
+  lp_pin_all(A0); lp_pin_all(B0);
+#undef V3D_LMMA
+  __syncthreads();
+
+  // ---- epilogue (the code of gemm256x256_kernel): two halves of WROWS rows through a padded LDS C tile, whole row segments out ----
+  constexpr int CROW = LBN * 2 + 16;
+  constexpr int TPR = LBN / 8;                            // threads per C row (16 bytes each)
+  constexpr int RPP = (BIG ? 512 : 256) / TPR;            // rows per pass
+  const T* bias = (const T*)p.bias;
+  T* out = (T*)p.out;
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    if (wm == half) {
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) {
+        const int nl = wn * 64 + ni * 16 + 4 * (lane >> 4);
+        float bv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (epi_has_bias(EPI)) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) bv[r] = to_f32(bias[n0 + nl + r]);
+        }
+#pragma unroll
+        for (int mi = 0; mi < MT; ++mi) {
+          const int ml = mi * 16 + (lane & 15);
+          uint2 pk;
+          pk.x = pack2<T>(acc[ni][mi][0] + bv[0], acc[ni][mi][1] + bv[1]);
+          pk.y = pack2<T>(acc[ni][mi][2] + bv[2], acc[ni][mi][3] + bv[3]);
+          *reinterpret_cast<uint2*>(smem + ml * CROW + nl * 2) = pk;
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    }
+    __syncthreads();
+    for (int row = tid / TPR; row < WROWS; row += RPP) {
+      const int ch = tid % TPR;
+      const int gm = m0 + half * WROWS + row;
+      if (gm < p.M) {
+        uint4 c = *reinterpret_cast<const uint4*>(smem + row * CROW + ch * 16);
+        if (EPI == EPI_BIAS_RES || EPI == EPI_RES) {
+          float v[8];
+          const int64_t rm = p.res_mod > 0 ? (gm % p.res_mod) : gm;
+          const uint4 rr = *reinterpret_cast<const uint4*>((const T*)p.res + rm * p.ldr + n0 + ch * 8);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] = vec_get<T>(c, j) + vec_get<T>(rr, j);
+          c = vec_pack<T>(v);
+        }
+        *reinterpret_cast<uint4*>(out + (int64_t)gm * p.ldo + n0 + ch * 8) = c;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+static int gemm_layout_tile() {   // 0 = by the cost model, 128 / 256 = force that tile form; read per call (tests, A/B runs)
+  const char* e = getenv("V3D_GEMM_LAYOUT_TILE");
+  return e ? atoi(e) : 0;
+}
+
+// Tile form by gemm_plan's constants for the 128 x 128 kernel and the 256 x 256 v3 kernel (the schedule this one shares).
+static bool gemm_layout_big(int M, int N, int K) {
+  if (N % B3N != 0) return false;
+  const double ks = (double)((K + BK - 1) / BK);
+  const int tiles256 = ((M + 255) / 256) * (N / B3N), tiles128 = ((M + BM - 1) / BM) * (N / BN);
+  const int r1 = (tiles128 + 511 - 25) / 512;
+  return (double)((tiles256 + 255) / 256) * (9.0 + 1.36 * ks) < (double)(r1 > 0 ? r1 : 1) * (1.0 + 0.98 * ks);
+}
+
+template <typename T, int EPI, bool AKM, bool BKM, bool BIG>
+static int launch_gemm_layout_one(GemmArgs p, hipStream_t st) {
+  constexpr int LBM = BIG ? 256 : 128, LBN = BIG ? 256 : 128, LDS = BIG ? GEMM3_LDS_BYTES : GEMM_LDS_BYTES;
+  p.tiles_m = (p.M + LBM - 1) / LBM;
+  p.tiles_n = p.N / LBN;
+  auto k = gemm_layout_kernel<T, EPI, AKM, BKM, BIG>;
+  static bool attr_done = false;
+  if (!attr_done) {
+    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    if (e != hipSuccess) { set_error("v3d_gemm_layout: LDS attribute: %s", hipGetErrorString(e)); return V3D_E_LAUNCH; }
+    attr_done = true;
+  }
+  hipLaunchKernelGGL(k, dim3(p.tiles_m * p.tiles_n), dim3(BIG ? 512 : 256), LDS, st, p);
+  return check_launch("v3d_gemm_layout");
+}
+
+template <typename T, int EPI>
+static int launch_gemm_layout(const GemmArgs& p, bool akm, bool bkm, bool big, hipStream_t st) {
+#define V3D_LAYOUT_CASE(A, B)                                                                             \
+  if (akm == A && bkm == B) return big ? launch_gemm_layout_one<T, EPI, A, B, true>(p, st) : launch_gemm_layout_one<T, EPI, A, B, false>(p, st);
+  V3D_LAYOUT_CASE(false, true)
+  V3D_LAYOUT_CASE(true, true)
+  V3D_LAYOUT_CASE(true, false)
+#undef V3D_LAYOUT_CASE
+  set_error("v3d_gemm_layout: no kernel for this layout");
+  return V3D_E_INVALID;
+}
+
 }  // namespace v3d
 
 using namespace v3d;
@@ -1451,4 +1751,44 @@ extern "C" int v3d_gemm(const void* A, int64_t lda, const void* W, int64_t ldw, 
   hipStream_t st = (hipStream_t)stream;
   if (M <= 8) return dtype == V3D_BF16 ? launch_gemv<bf16_t>(p, epilogue, st) : launch_gemv<f16_t>(p, epilogue, st);
   return dtype == V3D_BF16 ? launch_gemm<bf16_t>(p, epilogue, st) : launch_gemm<f16_t>(p, epilogue, st);
+}
+
+extern "C" int v3d_gemm_layout(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb, int b_kmajor,
+                               const void* bias, const void* res, int64_t ldr, int res_mod, void* out, int64_t ldo,
+                               int M, int N, int K, int dtype, int epilogue, void* stream) {
+  V3D_REQUIRE((a_kmajor == 0 || a_kmajor == 1) && (b_kmajor == 0 || b_kmajor == 1), "v3d_gemm_layout: a_kmajor=%d and b_kmajor=%d must be 0 or 1", a_kmajor, b_kmajor);
+  if (!a_kmajor && !b_kmajor) return v3d_gemm(A, lda, B, ldb, bias, res, ldr, res_mod, out, ldo, M, N, K, dtype, epilogue, stream);
+  V3D_REQUIRE(A, "v3d_gemm_layout: A is a null pointer");
+  V3D_REQUIRE(B, "v3d_gemm_layout: B is a null pointer");
+  V3D_REQUIRE(out, "v3d_gemm_layout: out is a null pointer");
+  V3D_REQUIRE(dtype == V3D_F16 || dtype == V3D_BF16, "v3d_gemm_layout: dtype must be f16 or bf16");
+  V3D_REQUIRE(M > 0 && N > 0 && K > 0, "v3d_gemm_layout: bad shape M=%d N=%d K=%d", M, N, K);
+  V3D_REQUIRE(N % BN == 0, "v3d_gemm_layout: N=%d must be a multiple of %d", N, BN);
+  V3D_REQUIRE((a_kmajor && b_kmajor) || K % BK == 0, "v3d_gemm_layout: K=%d must be a multiple of %d unless both operands are k-major", K, BK);
+  V3D_REQUIRE(!a_kmajor || M % 8 == 0, "v3d_gemm_layout: M=%d must be a multiple of 8 for a k-major A", M);
+  V3D_REQUIRE(lda % 8 == 0 && lda >= (a_kmajor ? M : K), "v3d_gemm_layout: lda=%lld must be a multiple of 8 and >= %s=%d", (long long)lda, a_kmajor ? "M" : "K", a_kmajor ? M : K);
+  V3D_REQUIRE(ldb % 8 == 0 && ldb >= (b_kmajor ? N : K), "v3d_gemm_layout: ldb=%lld must be a multiple of 8 and >= %s=%d", (long long)ldb, b_kmajor ? "N" : "K", b_kmajor ? N : K);
+  V3D_REQUIRE(ldo % 8 == 0 && ldo >= N, "v3d_gemm_layout: ldo=%lld must be a multiple of 8 and >= N=%d", (long long)ldo, N);
+  V3D_REQUIRE(aligned16(A), "v3d_gemm_layout: A must be 16-byte aligned");
+  V3D_REQUIRE(aligned16(B), "v3d_gemm_layout: B must be 16-byte aligned");
+  V3D_REQUIRE(aligned16(out), "v3d_gemm_layout: out must be 16-byte aligned");
+  V3D_REQUIRE(epilogue == EPI_NONE || epilogue == EPI_RES, "v3d_gemm_layout: epilogue %d is not available with a k-major operand (EPI_NONE and EPI_RES are)", epilogue);
+  V3D_REQUIRE(epilogue != EPI_RES || (res && aligned16(res) && ldr % 8 == 0 && ldr >= N), "v3d_gemm_layout: epilogue %d needs a 16-byte aligned res with ldr a multiple of 8 and >= N", epilogue);
+  // the kernels address an operand with 32-bit element offsets (a k-major tile spans 64 k-rows even where K is shorter)
+  const int64_t a_rows = a_kmajor ? (K > BK ? K : BK) : M, b_rows = b_kmajor ? (K > BK ? K : BK) : N;
+  V3D_REQUIRE(a_rows * lda < (1ll << 31), "v3d_gemm_layout: A is larger than 2^31 elements (4 GiB)");
+  V3D_REQUIRE(b_rows * ldb < (1ll << 31), "v3d_gemm_layout: B is larger than 2^31 elements (4 GiB)");
+  const int force = gemm_layout_tile();
+  V3D_REQUIRE(force == 0 || force == 128 || (force == 256 && N % B3N == 0), "v3d_gemm_layout: V3D_GEMM_LAYOUT_TILE=%d does not fit N=%d (0, 128, or 256 with N %% 256 == 0)", force, N);
+  GemmArgs p;
+  p.A = A; p.W = B; p.bias = nullptr; p.res = epilogue == EPI_RES ? res : nullptr; p.out = out;
+  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldb; p.ldr = ldr; p.ldo = ldo; p.res_mod = res_mod;
+  p.tiles_m = 0; p.tiles_n = 0; p.skew = 0; p.dma_late = 0; p.tile_base = 0; p.tile_count = 0;
+  p.sk_dp = -1; p.sk_split = 1; p.sk_ws = nullptr; p.sk_flags = nullptr; p.sk_epoch = 0;
+  const bool big = force == 256 || (force == 0 && gemm_layout_big(M, N, K));
+  hipStream_t st = (hipStream_t)stream;
+  const bool a = a_kmajor != 0, b = b_kmajor != 0;
+  if (dtype == V3D_BF16)
+    return epilogue == EPI_RES ? launch_gemm_layout<bf16_t, EPI_RES>(p, a, b, big, st) : launch_gemm_layout<bf16_t, EPI_NONE>(p, a, b, big, st);
+  return epilogue == EPI_RES ? launch_gemm_layout<f16_t, EPI_RES>(p, a, b, big, st) : launch_gemm_layout<f16_t, EPI_NONE>(p, a, b, big, st);
 }

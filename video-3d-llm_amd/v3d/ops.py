@@ -329,6 +329,34 @@ def gemm(a, w, bias=None, res=None, epilogue=EPI_NONE, out=None, res_mod=0):
     return out
 
 
+def gemm_layout(a, b, a_kmajor=False, b_kmajor=False, res=None, epilogue=EPI_NONE, out=None):
+    """out [M, N] = epilogue(op(a) @ op(b).T) on the tensors as stored: a is [M, K] (a_kmajor False) or [K, M] (True), b is [N, K] or
+    [K, N]; the last dimension of each is contiguous, the row stride may exceed it.  (False, True) is dx = dy @ W for an nn.Linear
+    weight W [out, in], (True, True) dW = dy.T @ x.  Epilogues with a k-major operand: EPI_NONE, EPI_RES (include/v3d.h: v3d_gemm_layout)."""
+    if not a.is_cuda or not b.is_cuda:
+        raise V3DError("gemm_layout operands must live in HBM")
+    if a.dim() != 2 or b.dim() != 2 or a.stride(-1) != 1 or b.stride(-1) != 1:
+        raise V3DError("gemm_layout operands must be matrices with a contiguous last dimension")
+    if a.dtype != b.dtype:
+        raise V3DError(f"gemm_layout: a is {a.dtype} but b is {b.dtype}")
+    (K, M) = a.shape if a_kmajor else a.shape[::-1]
+    (Kb, N) = b.shape if b_kmajor else b.shape[::-1]
+    if Kb != K:
+        raise V3DError(f"gemm_layout: a {tuple(a.shape)} (a_kmajor={bool(a_kmajor)}) has K = {K} but b {tuple(b.shape)} "
+                       f"(b_kmajor={bool(b_kmajor)}) has K = {Kb}")
+    if out is None:
+        out = torch.empty((M, N), dtype=a.dtype, device=a.device)
+    _rows_fit(out, M, N, a.dtype, "gemm_layout")
+    if res is not None and (res.dim() != 2 or res.shape[0] < M or res.shape[1] < N or res.dtype != a.dtype):
+        raise V3DError(f"gemm_layout: res {tuple(res.shape)} {res.dtype} does not cover the output [{M},{N}] {a.dtype}")
+    if epilogue == EPI_RES and res is None:
+        raise V3DError("gemm_layout: EPI_RES needs res")
+    check(lib().v3d_gemm_layout(_p(a), a.stride(0), int(bool(a_kmajor)), _p(b), b.stride(0), int(bool(b_kmajor)), None, _p(res),
+                                res.stride(0) if res is not None else 0, 0, _p(out), out.stride(0), M, N, K, _code(a),
+                                epilogue, _stream()), "v3d_gemm_layout")
+    return out
+
+
 def interleave_gate_up(wg, wu):
     """Row order v3d_gemm's SWIGLU epilogue expects: per 128-row tile, 64 gate rows then the 64 up rows."""
     I, K = wg.shape

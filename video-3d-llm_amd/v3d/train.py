@@ -67,6 +67,24 @@ class _wgrad_overlap:
         return False
 
 
+def _gemm_layouts():
+    """V3D_TRAIN_GEMM_LAYOUTS=1 (default off; read per call): linear_backward runs dx and dW on ops.gemm_layout, on w, dy and x as they
+    are stored - no transposed copies, no padding of the token rows."""
+    return os.environ.get("V3D_TRAIN_GEMM_LAYOUTS", "0") == "1"
+
+
+def _layout_fits(a, b, a_kmajor, b_kmajor):
+    """Would v3d_gemm_layout take these operands (include/v3d.h)?  Where it would not, linear_backward keeps the transposing path."""
+    (K, M) = a.shape if a_kmajor else a.shape[::-1]
+    (Kb, N) = b.shape if b_kmajor else b.shape[::-1]
+    if Kb != K or N % 128 or (K % 64 and not (a_kmajor and b_kmajor)) or (a_kmajor and M % 8):
+        return False
+    for t in (a, b):
+        if t.stride(1) != 1 or t.stride(0) % 8 or t.data_ptr() % 16 or max(t.shape[0], 64) * t.stride(0) >= 2 ** 31:
+            return False
+    return True
+
+
 def _weight_grads(x, dy, need_dw, need_db):
     """dW = dy^T . x as gemm(dy^T [N, Mp], x^T [K, Mp]) and db = column sums of dy.  Shapes are padded for the product's tiling, never
     its value: the token rows (the k dimension) to 128, i.e. an EVEN number of 64-wide K-steps, which the 256 x 256 kernel's split-K
@@ -78,9 +96,13 @@ def _weight_grads(x, dy, need_dw, need_db):
     if need_dw:
         M, K = x.shape
         Mp = (M + 127) // 128 * 128
-        dyt = ops.transpose(dy, out_cols=Mp)                          # [N, Mp]
         Kp = (K + 255) // 256 * 256
-        if Kp != K and M >= 8192 and (Kp - K) * 8 <= K:
+        tail = Kp != K and M >= 8192 and (Kp - K) * 8 <= K
+        if _gemm_layouts() and not tail and _layout_fits(dy, x, True, True):
+            dw = ops.gemm_layout(dy, x, a_kmajor=True, b_kmajor=True)             # [N, K], the token rows are the k dimension as they lie
+            return dw, ops.colsum(dy) if need_db else None
+        dyt = ops.transpose(dy, out_cols=Mp)                          # [N, Mp]
+        if tail:
             xt = torch.empty((Kp, Mp), dtype=x.dtype, device=x.device)
             xt[K:].zero_()
             ops.transpose(x, out_cols=Mp, out=xt[:K])
@@ -110,8 +132,12 @@ def linear_backward(x, w, dy, res=None, need_dx=True, need_dw=True, need_db=Fals
             if t is not None:
                 t.record_stream(main)                                 # read (optimizer, accumulation) and freed on the caller's stream
     if need_dx:
-        wt = ops.transpose(w)                                         # [K, N]
-        dx = ops.gemm(dy, wt, res=res, epilogue=ops.EPI_RES if res is not None else ops.EPI_NONE)
+        epi = ops.EPI_RES if res is not None else ops.EPI_NONE
+        if _gemm_layouts() and _layout_fits(dy, w, False, True):
+            dx = ops.gemm_layout(dy, w, b_kmajor=True, res=res, epilogue=epi)     # w [N, K] is dx's B operand in k-major form
+        else:
+            wt = ops.transpose(w)                                     # [K, N]
+            dx = ops.gemm(dy, wt, res=res, epilogue=epi)
     if side is None and (need_dw or need_db):
         dw, db = _weight_grads(x, dy, need_dw, need_db)
     return dx, dw, db
