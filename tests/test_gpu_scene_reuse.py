@@ -19,6 +19,45 @@ def _engine(seed=31, dtype=torch.bfloat16):
     return Engine(cfg, sd, dtype=dtype, device="cuda", max_frames=2)
 
 
+def _answer_margins(eng, q, steps, force=None):
+    """Engine.answer's launches on the current (prefilled) context, keeping per step the top-2 logit margin relative to the largest
+    |logit| (tests/test_gpu_engine.py::_single_decode_with_margins).  force: token ids fed back instead of the loop's own, so that the
+    margins are those of answer()'s kernels along another run's tokens.  -> (tokens, margins)"""
+    from v3d import ops
+    P = eng.ctx.prefix_len
+    qd = q.cuda()
+    Q = qd.numel()
+    x = ops.embed_gather(eng.embed, qd, out=eng.l_x[P: P + Q])
+    logits = eng.llm_forward(x, P, last_rows=[Q - 1])
+    toks, mg = [], []
+    for st in range(steps):
+        top2 = torch.topk(logits.float(), 2).values
+        mg.append(((top2[0] - top2[1]) / logits.float().abs().max()).item())
+        tok = torch.zeros(1, dtype=torch.int64, device="cuda")
+        ops.argmax(logits, tok)
+        toks.append(int(tok))
+        if force is not None:
+            tok = force[st: st + 1].cuda()
+        if st + 1 < steps:
+            xe = ops.embed_gather(eng.embed, tok, out=eng.l_x[P + Q + st: P + Q + st + 1])
+            logits = eng.decode_forward(xe, P + Q + st)
+    return toks, mg
+
+
+def _assert_flips_are_near_ties(eng, questions, rows_a, rows_b, steps, alone=None):
+    """The project's margin rule for every question whose tokens differ between rows_a and rows_b: at the first differing
+    step, the top-2 margin of answer()'s own logits - along rows_a's tokens - is below 0.02 of the largest |logit|.  alone: answer()'s
+    tokens where rows_a are those (the replica of its launches must then reproduce them)."""
+    for gi, (q, a, b) in enumerate(zip(questions, rows_a, rows_b)):
+        if torch.equal(a, b):
+            continue
+        toks, margins = _answer_margins(eng, q, steps, force=None if alone is not None else a)
+        if alone is not None:
+            assert toks == alone[gi].tolist(), "the replica of answer()'s launches gave other tokens than answer()"
+        first = next(st for st in range(steps) if int(a[st]) != int(b[st]))
+        assert margins[first] < 0.02, (gi, first, a.tolist(), b.tolist(), margins[first])
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 def test_cached_answers_equal_uncached_generate(dtype):
     eng = _engine(dtype=dtype)
@@ -115,6 +154,7 @@ def test_answer_group_equals_answering_alone(dtype):
         assert torch.equal(rev[len(questions) - 1 - gi], together[gi])
     same = sum(int(torch.equal(a, b)) for a, b in zip(alone, together))
     assert same >= len(questions) - 2, (alone, together)                  # near-ties may flip a token of a question or two
+    _assert_flips_are_near_ties(eng, questions, alone, together, steps, alone=alone)          # ... and only a near-tie may
     assert all(t.shape == (steps,) for t in together)
     # the decode attention reads the shared prefix rows from ONE copy for every question (default; r04: one matrix-core launch over the
     # prefix for all questions): the tokens of every question reading its own copy of them, up to near-ties (the r03 form, which walks
@@ -132,6 +172,7 @@ def test_answer_group_equals_answering_alone(dtype):
     for a, b in zip(own, r03):
         assert torch.equal(a, b)
     assert sum(int(torch.equal(a, b)) for a, b in zip(own, together)) >= len(questions) - 1, (own, together)
+    _assert_flips_are_near_ties(eng, questions, together, own, steps)
     eos = int(together[2][1])
     cut = eng.answer_group(questions, max_new_tokens=steps, eos_token_id=eos)
     for a, b in zip(cut, together):
