@@ -109,6 +109,7 @@ CASES = [
     (300, 512, 3584, "bias"),
     (513, 512, 1024, "swiglu"),
     (300, 256, 18944, "res"),
+    (2305, 512, 256, "swiglu"),     # ten m-tiles (short last group of 8), 20 workgroups (XCD remainder), one-row M tail, two K-steps, two n-tiles
 ]
 
 

@@ -56,6 +56,7 @@ CASES = [
     (1000, 1024, 18944, "res"),
     (513, 2048, 3584, "swiglu"),
     (6794, 4608, 3584, "bias"),
+    (2305, 512, 256, "swiglu"),     # ten m-tiles (short last group of 8), 20 workgroups (XCD remainder), one-row M tail, two K-steps, two n-tiles
 ]
 
 

@@ -19,303 +19,29 @@
 // v_cvt_scalef32_pk_{bf16,f16,f32}_fp4(src, scale, sel) widens byte `sel` of src: element 0 is the low nibble, element 1 the
 // high nibble, multiplied by 2^(exponent field of scale - 127) (the mantissa of the scale is ignored).
 //
-// Prefill kernel = gemm_fp8_kernel's structure: 256 x 256 tile, K-step 128, 8 waves of 128 x 64, DMA staging, four phases of
-// 8 MFMAs, one barrier per K-step.  The activation tile keeps its 128-byte rows and XOR swizzle; the weight tile has 64-byte
-// rows (4 chunks of 16 bytes, chunk ^ ((row >> 2) & 3): the 16 rows that read one chunk together spread over all banks), so a
-// stage is 48 KiB instead of 64 and a weight fragment is ONE ds_read_b128.  The 32 KiB that frees stays unused (the epilogue
-// needs 64 KiB, two stages give 96).  Measured once (profiles/fp4_linears.txt) this kernel takes 1.06-1.12 x gemm_fp8_kernel's time;
+// Prefill kernel = the shared tile of gemm_q8_tile.h (schedule, epilogue, launch and argument checks live there) with the WfMxfp4
+// weight format.  The activation tile keeps its 128-byte rows and XOR swizzle; the weight tile has 64-byte rows (4 chunks of 16
+// bytes, chunk ^ ((row >> 2) & 3): the 16 rows that read one chunk together spread over all banks), so a stage is 48 KiB instead of
+// 64 and a weight fragment is ONE ds_read_b128.  The 32 KiB that frees stays unused (the epilogue needs 64 KiB, two stages give 96).
+// Measured once (profiles/fp4_linears.txt) this kernel takes 1.06-1.12 x gemm_fp8_kernel's time;
 // only those end-to-end times were measured, no counters.  HYPOTHESIS, not measured: the four block exponents a lane fetches per
 // K-step are single-byte global loads at a row stride of lde (uncoalesced, issued beside the MFMA phases) and cost more than the
 // halved weight staging saves.  FOLLOW-UP (open, not a closed design): stage the K-step's [256 x 4] exponent tile (1 KiB) through
 // LDS with the weight DMA, or repack the exponents at load so that a lane's four bytes are one dword; the freed LDS also allows
 // a third stage.
-#include "v3d_common.h"
+#include "gemm_q8_tile.h"
 
 namespace v3d {
 
-using f4_v8i = __attribute__((ext_vector_type(8))) int;
-using f4_v4i = __attribute__((ext_vector_type(4))) int;
 using f4_f32x4 = __attribute__((ext_vector_type(4))) float;
 using f4_f32x2 = __attribute__((ext_vector_type(2))) float;
 
-constexpr int F4_BK = 128;                               // k elements per K-step
-constexpr int F4_ATILE = 256 * F4_BK;                    // e4m3 activations: 32 KiB
-constexpr int F4_WROW = F4_BK / 2;                       // 64 bytes of codes per weight row per K-step
-constexpr int F4_WTILE = 256 * F4_WROW;                  // 16 KiB
-constexpr int F4_STAGE = F4_ATILE + F4_WTILE;
-constexpr int F4_LDS = 2 * F4_STAGE;                     // 96 KiB
-constexpr int F4_BN = 256;
-
-enum { F4_EPI_NONE = 0, F4_EPI_BIAS = 1, F4_EPI_RES = 5, F4_EPI_SWIGLU = 6 };
 enum { F4_DEC_NONE = 0, F4_DEC_BIAS = 1, F4_DEC_RES = 2, F4_DEC_SWIGLU = 3 };
 
-struct Fp4GemmArgs {
-  const uint8_t* A; const uint8_t* W; const uint8_t* E; const float* sa;
-  const void* bias; const void* res; void* out;
-  int M, N, K;
-  int64_t lda, ldw, lde, ldr, ldo;
-  int tiles_m, tiles_n;
-};
-
-__device__ __forceinline__ float silu4(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
 __device__ __forceinline__ float silu4_dec(float x) { return x / (1.0f + __expf(-x)); }
 
-__device__ __forceinline__ void glds16_f4(const void* gsrc, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ void tile_of_block4(int bid, int nblocks, int tiles_m, int tiles_n, int& tm, int& tn) {
-  const int q = nblocks >> 3, r = nblocks & 7, xcd = bid & 7;
-  const int L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  constexpr int GROUP_M = 8;
-  const int per_group = GROUP_M * tiles_n;
-  const int g = L / per_group, in_g = L - g * per_group;
-  const int first_m = g * GROUP_M;
-  const int gsz = (tiles_m - first_m) < GROUP_M ? (tiles_m - first_m) : GROUP_M;
-  tm = first_m + in_g % gsz;
-  tn = in_g / gsz;
-}
-
-// weight row of the [N, K] matrix behind row `row` of the 256-row tile.  SwiGLU (tile columns = two groups of [gate64 | up64]):
-// wave column row >> 6 gets the gate columns and the MATCHING up columns of one 32-wide output block (as gemm_fp8_kernel)
-template <int EPI>
-__device__ __forceinline__ int f4_wcol(int row) {
-  return EPI == F4_EPI_SWIGLU ? 128 * (row >> 7) + ((row & 32) ? 64 : 0) + 32 * ((row >> 6) & 1) + (row & 31) : row;
-}
-
 template <typename T, int EPI>
-__global__ __launch_bounds__(512, 2) void gemm_mxfp4_kernel(Fp4GemmArgs p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int MT = 8;
-  constexpr int MG = MT / 4;              // m-tiles per phase (4 phases)
-  constexpr int WROWS = MT * 16;
-  constexpr int BM = 2 * WROWS;
-  constexpr int APW = BM / 8 / 8;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
-  int tm, tn;
-  tile_of_block4(blockIdx.x, gridDim.x, p.tiles_m, p.tiles_n, tm, tn);
-  const int m0 = tm * BM, n0 = tn * F4_BN;
-
-  unsigned a_off[APW], w_off[2];
-#pragma unroll
-  for (int i = 0; i < APW; ++i) {
-    const int row = wave * (APW * 8) + i * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-    int gm = m0 + row;
-    gm = gm < p.M ? gm : p.M - 1;
-    a_off[i] = (unsigned)(gm * (int)p.lda + chunk * 16);
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {           // a DMA of the weight tile = 16 rows x 4 chunks
-    const int row = wave * 32 + i * 16 + (lane >> 2);
-    const int chunk = (lane & 3) ^ ((row >> 2) & 3);
-    w_off[i] = (unsigned)((n0 + f4_wcol<EPI>(row)) * (int)p.ldw + chunk * 16);
-  }
-  auto stage = [&](int buf, int kt) {
-    char* ba = smem + buf * F4_STAGE + (wave * APW * 8) * F4_BK;
-    char* bw = smem + buf * F4_STAGE + F4_ATILE + (wave * 32) * F4_WROW;
-    const char* Ak = (const char*)p.A + (size_t)kt * F4_BK;
-    const char* Wk = (const char*)p.W + (size_t)kt * F4_WROW;
-#pragma unroll
-    for (int i = 0; i < APW; ++i) glds16_f4(Ak + a_off[i], ba + i * 8 * F4_BK);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) glds16_f4(Wk + w_off[i], bw + i * 16 * F4_WROW);
-  };
-
-  // activation fragment = 32 bytes = logical chunks g and 4 + g of the lane's row (g = lane>>4, see the header); weight fragment =
-  // chunk g of its 64-byte row (16 bytes = the 32 codes of MX block g of this K-step)
-  const int l15 = lane & 15, g4 = lane >> 4;
-  const int sw = (lane >> 1) & 7;
-  const int frow = l15 * F4_BK;
-  const unsigned fo_lo = frow + (((g4) ^ sw) << 4), fo_hi = frow + (((g4 + 4) ^ sw) << 4);
-  const unsigned fo_w = l15 * F4_WROW + ((g4 ^ (l15 >> 2)) << 4);
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  const unsigned offA = lds0 + (wm * WROWS) * F4_BK, offW = lds0 + F4_ATILE + (wn * 64) * F4_WROW + fo_w;
-
-  // the lane's block exponent of n-tile ni at K-step kt: e[weight row][4 kt + g]
-  const uint8_t* eptr[4];
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) eptr[ni] = p.E + (int64_t)(n0 + f4_wcol<EPI>(wn * 64 + 16 * ni + l15)) * p.lde + g4;
-
-  f4_f32x4 acc[4][MT];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < MT; ++j) acc[i][j] = f4_f32x4{0.f, 0.f, 0.f, 0.f};
-
-  f4_v4i A0[MG][2], A1[MG][2], B0[4];
-  int sc[4], scn[4];
-#define F4_DSR(dst, addr, imm) asm volatile("ds_read_b128 %0, %1 offset:" #imm : "=v"(dst) : "v"(addr))
-#define F4_RDT(f, lo, hi, imm) { F4_DSR(f[0], lo, imm); F4_DSR(f[1], hi, imm); }
-#define F4_RD_A(F, lo, hi, tile0)                                                                                 \
-  {                                                                                                               \
-    if constexpr ((tile0) == 0) { F4_RDT(F[0], lo, hi, 0); F4_RDT(F[1], lo, hi, 2048); }                          \
-    else if constexpr ((tile0) == 2) { F4_RDT(F[0], lo, hi, 4096); F4_RDT(F[1], lo, hi, 6144); }                  \
-    else if constexpr ((tile0) == 4) { F4_RDT(F[0], lo, hi, 8192); F4_RDT(F[1], lo, hi, 10240); }                 \
-    else { F4_RDT(F[0], lo, hi, 12288); F4_RDT(F[1], lo, hi, 14336); }                                            \
-  }
-#define F4_RD_B(F, w) { F4_DSR(F[0], w, 0); F4_DSR(F[1], w, 1024); F4_DSR(F[2], w, 2048); F4_DSR(F[3], w, 3072); }
-#define F4_WA(cnt, F) asm volatile("s_waitcnt " cnt : "+v"(F[0][0]), "+v"(F[0][1]), "+v"(F[1][0]), "+v"(F[1][1]) : : "memory")
-#define F4_WAB(cnt, F, G)                                                                                          \
-  asm volatile("s_waitcnt " cnt : "+v"(F[0][0]), "+v"(F[0][1]), "+v"(F[1][0]), "+v"(F[1][1]), "+v"(G[0]), "+v"(G[1]), \
-               "+v"(G[2]), "+v"(G[3]) : : "memory")
-#define F4_FRAG(f) (f4_v8i{f[0][0], f[0][1], f[0][2], f[0][3], f[1][0], f[1][1], f[1][2], f[1][3]})
-#define F4_FRAGW(f) (__builtin_shufflevector(f, f, 0, 1, 2, 3, -1, -1, -1, -1))
-#define F4_MMA(FA, FB, tile0)                                                                                       \
-  {                                                                                                                 \
-    __builtin_amdgcn_s_setprio(1);                                                                                  \
-    _Pragma("unroll") for (int i = 0; i < MG; ++i)                                                                  \
-    _Pragma("unroll") for (int ni = 0; ni < 4; ++ni)                                                                \
-        acc[ni][(tile0) + i] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(F4_FRAGW(FB[ni]), F4_FRAG(FA[i]),   \
-                                                                                  acc[ni][(tile0) + i], 4, 0, 0, sc[ni], 0, 127); \
-    __builtin_amdgcn_s_setprio(0);                                                                                  \
-  }
-
-  const int nt = p.K / F4_BK;
-  stage(0, 0);
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) sc[ni] = eptr[ni][0];
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  for (int t = 0; t < nt; ++t) {
-    const int cur = t & 1;
-    const unsigned alo = offA + cur * F4_STAGE + fo_lo, ahi = offA + cur * F4_STAGE + fo_hi;
-    const unsigned wad = offW + cur * F4_STAGE;
-    F4_RD_B(B0, wad);
-    F4_RD_A(A0, alo, ahi, 0);
-    if (t + 1 < nt) {                                // buffer cur^1 was released by the barrier that ended step t-1
-      stage(cur ^ 1, t + 1);
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) scn[ni] = eptr[ni][4 * (t + 1)];
-    }
-    F4_RD_A(A1, alo, ahi, 2);
-    F4_WAB("lgkmcnt(4)", A0, B0);
-    F4_MMA(A0, B0, 0);
-    F4_RD_A(A0, alo, ahi, 4);
-    F4_WA("lgkmcnt(4)", A1);
-    F4_MMA(A1, B0, 2);
-    F4_RD_A(A1, alo, ahi, 6);
-    F4_WA("lgkmcnt(4)", A0);
-    F4_MMA(A0, B0, 4);
-    F4_WA("vmcnt(0) lgkmcnt(0)", A1);               // last fragments + this wave's share of tile t+1 and its exponents
-    F4_MMA(A1, B0, 6);
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) sc[ni] = scn[ni];
-    __builtin_amdgcn_s_barrier();                    // tile t fully read by everyone, tile t+1 visible
-  }
-  __syncthreads();
-
-  // epilogue as gemm_fp8_kernel (the block scales are already inside the accumulators: only sa[m] is left): each wave turns its
-  // 128 x 64 part of the C tile around in a private 8 KiB of LDS, 32 rows at a time; SwiGLU formed in registers first
-  const T* bias = (const T*)p.bias;
-  T* out = (T*)p.out;
-  {
-    int ln = lane;
-    asm volatile("" : "+v"(ln));
-    const int e15 = ln & 15, l4 = ln >> 4;
-    char* const reg = smem + wave * 8192;
-    if constexpr (EPI == F4_EPI_SWIGLU) {
-      constexpr int CP = 80;
-      const int rrow = ln >> 2, rch = ln & 3;
-      T* const obase = out + tn * 128 + (wn >> 1) * 64 + (wn & 1) * 32 + rch * 8;
-#pragma unroll
-      for (int q = 0; q < MT / 2; ++q) {
-#pragma unroll
-        for (int m2 = 0; m2 < 2; ++m2) {
-          const int mi = 2 * q + m2;
-          int gmc = m0 + wm * WROWS + 16 * mi + e15;
-          gmc = gmc < p.M ? gmc : p.M - 1;
-          const float sa = p.sa[gmc];
-#pragma unroll
-          for (int n2 = 0; n2 < 2; ++n2) {
-            float v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              v[r] = round_to<T>(silu4(round_to<T>(acc[n2][mi][r] * sa))) * round_to<T>(acc[2 + n2][mi][r] * sa);
-            uint2 pk;
-            pk.x = pack2<T>(v[0], v[1]); pk.y = pack2<T>(v[2], v[3]);
-            *reinterpret_cast<uint2*>(reg + (m2 * 16 + e15) * CP + (16 * n2 + 4 * l4) * 2) = pk;
-          }
-        }
-        uint4 cq[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) cq[j] = *reinterpret_cast<const uint4*>(reg + (rrow + 16 * j) * CP + rch * 16);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int gm = m0 + wm * WROWS + 32 * q + rrow + 16 * j;
-          if (gm < p.M) *reinterpret_cast<uint4*>(obase + (int64_t)gm * p.ldo) = cq[j];
-        }
-      }
-    } else {
-      constexpr int CP = 144;
-      const int rrow = ln >> 3, rch = ln & 7;
-      const int colr = n0 + wn * 64 + rch * 8;
-      float bv[4][4];
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int c = n0 + wn * 64 + 16 * ni + 4 * l4 + r;
-          bv[ni][r] = bias != nullptr ? to_f32(bias[c]) : 0.f;
-        }
-#pragma unroll
-      for (int q = 0; q < MT / 2; ++q) {
-        uint4 rr[4];
-        if constexpr (EPI == F4_EPI_RES) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            int gc = m0 + wm * WROWS + 32 * q + rrow + 8 * j;
-            gc = gc < p.M ? gc : p.M - 1;
-            rr[j] = *reinterpret_cast<const uint4*>((const T*)p.res + (int64_t)gc * p.ldr + colr);
-          }
-        }
-#pragma unroll
-        for (int m2 = 0; m2 < 2; ++m2) {
-          const int mi = 2 * q + m2;
-          int gmc = m0 + wm * WROWS + 16 * mi + e15;
-          gmc = gmc < p.M ? gmc : p.M - 1;
-          const float sa = p.sa[gmc];
-#pragma unroll
-          for (int ni = 0; ni < 4; ++ni) {
-            uint2 pk;
-            pk.x = pack2<T>(acc[ni][mi][0] * sa + bv[ni][0], acc[ni][mi][1] * sa + bv[ni][1]);
-            pk.y = pack2<T>(acc[ni][mi][2] * sa + bv[ni][2], acc[ni][mi][3] * sa + bv[ni][3]);
-            *reinterpret_cast<uint2*>(reg + (m2 * 16 + e15) * CP + (16 * ni + 4 * l4) * 2) = pk;
-          }
-        }
-        uint4 cq[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) cq[j] = *reinterpret_cast<const uint4*>(reg + (rrow + 8 * j) * CP + rch * 16);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          uint4 c = cq[j];
-          const int gm = m0 + wm * WROWS + 32 * q + rrow + 8 * j;
-          if constexpr (EPI == F4_EPI_RES) {
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = vec_get<T>(c, e) + vec_get<T>(rr[j], e);
-            c = vec_pack<T>(v);
-          }
-          if (gm < p.M) *reinterpret_cast<uint4*>(out + (int64_t)gm * p.ldo + colr) = c;
-        }
-      }
-    }
-  }
-#undef F4_DSR
-#undef F4_RDT
-#undef F4_RD_A
-#undef F4_RD_B
-#undef F4_WA
-#undef F4_WAB
-#undef F4_FRAG
-#undef F4_FRAGW
-#undef F4_MMA
-}
+__global__ __launch_bounds__(512, 2) void gemm_mxfp4_kernel(Q8GemmArgs p) { q8_gemm_tile<T, EPI, WfMxfp4>(p); }
 
 // MXFP4 quantiser.  Per block of 32 k: e = clamp(floor(log2(amax)) - 2 + 127, 0, 254) (127 for an all-zero block) - for a finite
 // 16-bit input that is the f32 exponent field of amax minus 2, clamped below; elements are w * 2^(127 - e) (exact) rounded to
@@ -588,29 +314,9 @@ __global__ __launch_bounds__(512) void linear_decode_mxfp4_mfma_kernel(const T* 
 }
 
 template <typename T>
-static int launch_mxfp4(Fp4GemmArgs p, int epi, hipStream_t st) {
-  p.tiles_m = (p.M + 255) / 256;
-  p.tiles_n = p.N / F4_BN;
-#define F4_CASE(E)                                                                                        \
-  case E: {                                                                                               \
-    auto k = gemm_mxfp4_kernel<T, E>;                                                                     \
-    static bool attr_done = false;                                                                        \
-    if (!attr_done) {                                                                                     \
-      hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, F4_LDS); \
-      if (e != hipSuccess) { set_error("v3d_gemm_mxfp4: LDS attribute: %s", hipGetErrorString(e)); return V3D_E_LAUNCH; } \
-      attr_done = true;                                                                                   \
-    }                                                                                                     \
-    hipLaunchKernelGGL(k, dim3(p.tiles_m * p.tiles_n), dim3(512), F4_LDS, st, p);                         \
-  } break;
-  switch (epi) {
-    F4_CASE(F4_EPI_NONE)
-    F4_CASE(F4_EPI_BIAS)
-    F4_CASE(F4_EPI_RES)
-    F4_CASE(F4_EPI_SWIGLU)
-    default: set_error("v3d_gemm_mxfp4: epilogue %d unsupported (NONE, BIAS, RES, SWIGLU)", epi); return V3D_E_INVALID;
-  }
-#undef F4_CASE
-  return check_launch("v3d_gemm_mxfp4");
+static int launch_mxfp4(const Q8GemmArgs& p, int epi, hipStream_t st) {
+  return q8_launch<q8_lds_bytes<WfMxfp4>, gemm_mxfp4_kernel<T, Q8_EPI_NONE>, gemm_mxfp4_kernel<T, Q8_EPI_BIAS>, gemm_mxfp4_kernel<T, Q8_EPI_RES>,
+                   gemm_mxfp4_kernel<T, Q8_EPI_SWIGLU>>(p, epi, "v3d_gemm_mxfp4", st);
 }
 
 }  // namespace v3d
@@ -636,18 +342,8 @@ extern "C" int v3d_quantize_mxfp4_rows(const void* w, int64_t ldw, int64_t rows,
 extern "C" int v3d_gemm_mxfp4(const void* A, int64_t lda, const float* scale_a, const void* Wq, int64_t ldw, const void* We, int64_t lde,
                               const void* bias, const void* res, int64_t ldr, void* out, int64_t ldo, int M, int N, int K, int out_dtype,
                               int epilogue, void* stream) {
-  V3D_REQUIRE(A && Wq && We && scale_a && out, "v3d_gemm_mxfp4: null pointer");
-  V3D_REQUIRE(out_dtype == V3D_F16 || out_dtype == V3D_BF16, "v3d_gemm_mxfp4: output dtype must be f16 or bf16");
-  V3D_REQUIRE(M > 0 && N > 0 && K > 0 && N % F4_BN == 0 && K % F4_BK == 0, "v3d_gemm_mxfp4: N=%d must be a multiple of 256 and K=%d of 128", N, K);
-  V3D_REQUIRE(lda >= K && ldw >= K / 2 && lde >= K / 32 && lda % 16 == 0 && ldw % 16 == 0 && ldo % 8 == 0, "v3d_gemm_mxfp4: leading dimensions");
-  V3D_REQUIRE(aligned16(A) && aligned16(Wq) && aligned16(out), "v3d_gemm_mxfp4: pointers must be 16-byte aligned");
-  V3D_REQUIRE((int64_t)M * lda < (1ll << 31) && (int64_t)N * ldw < (1ll << 31), "v3d_gemm_mxfp4: operand larger than 2 GiB");
-  V3D_REQUIRE(epilogue != F4_EPI_BIAS || bias, "v3d_gemm_mxfp4: bias epilogue without bias");
-  V3D_REQUIRE(epilogue != F4_EPI_RES || (res && aligned16(res) && ldr % 8 == 0), "v3d_gemm_mxfp4: residual epilogue without residual");
-  Fp4GemmArgs p;
-  p.A = (const uint8_t*)A; p.W = (const uint8_t*)Wq; p.E = (const uint8_t*)We; p.sa = scale_a;
-  p.bias = epilogue == F4_EPI_BIAS ? bias : nullptr; p.res = epilogue == F4_EPI_RES ? res : nullptr; p.out = out;
-  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.lde = lde; p.ldr = ldr; p.ldo = ldo;
+  const Q8GemmArgs p{(const uint8_t*)A, (const uint8_t*)Wq, (const uint8_t*)We, scale_a, nullptr, bias, res, out, M, N, K, lda, ldw, lde, ldr, ldo, 0, 0};
+  if (int rc = q8_validate("v3d_gemm_mxfp4", p, We != nullptr, ldw >= K / 2 && lde >= K / 32, out_dtype, epilogue)) return rc;
   hipStream_t st = (hipStream_t)stream;
   return out_dtype == V3D_BF16 ? launch_mxfp4<bf16_t>(p, epilogue, st) : launch_mxfp4<f16_t>(p, epilogue, st);
 }
