@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define V3D_ABI_VERSION 7   /* 2: *_rows decode entries, fp8 path, a7 / a3 device entries; 3: rope_kv_store, add_row, ...; 4: resize_bicubic, eos_update, embed_grad bounds; 6: sumsq, *_rows entries take 1..32 rows; 7: attention_shared_prefix */
+#define V3D_ABI_VERSION 7   /* 2: *_rows decode entries, fp8 path, a7 / a3 device entries; 3: rope_kv_store, add_row, ...; 4: resize_bicubic, eos_update, embed_grad bounds; 6: sumsq, *_rows entries take 1..32 rows; 7: attention_shared_prefix; ground_scores_rows and add_rows were ADDED under 7 (no entry changed) */
 
 enum { V3D_F32 = 0, V3D_F16 = 1, V3D_BF16 = 2 };
 enum { V3D_U8_HWC = 16 };   /* v3d_resize_bicubic_u8 only: 8-bit interleaved output, no normalisation */
@@ -255,6 +255,14 @@ int v3d_rope_kv_store(void* qkv, int64_t ldx, int64_t tokens, int n_q_heads, int
  * rows: device int64 [n_rows]; 16-bit dtypes; the sum is rounded once to dtype. */
 int v3d_add_row(void* x, int64_t ldx, const int64_t* rows, int n_rows, int C, const void* add, int dtype, void* stream);
 
+/* The same add with one source row per destination row: x[rows[i], 0:C] += add[src[i], 0:C] (add: [*, lda]) - the box-centre PEs of a
+ * batch of Scan2Cap questions on their <coord> rows in one launch.  rows, src: device int64 [n_rows].  rows must be DISTINCT (each
+ * destination row belongs to one workgroup; a repeated row is a race); src may repeat (two <coord> tokens of one question take the
+ * same PE).  Any C > 0, ldx, lda >= C: 16-byte accesses where ldx % 8 == lda % 8 == 0 and both bases are 16-byte aligned, the
+ * columns past 8 floor(C / 8) (or all of them) one by one.  With every src equal it is v3d_add_row bit for bit. */
+int v3d_add_rows(void* x, int64_t ldx, const int64_t* rows, const int64_t* src, int n_rows, int C, const void* add, int64_t lda,
+                 int dtype, void* stream);
+
 /* ------------------------------------------------------------------ attention ----------- */
 
 /* K16 / K11  softmax(Q K^T * scale [+ causal mask]) V without materialising the scores.
@@ -399,6 +407,13 @@ int v3d_masked_mean(const void* feat, const uint8_t* mask, int n_obj, int T, int
 /* K20  predict_box 'infonce', llava_qwen.py:298-300: scores[i] = <normalize(obj[i]), normalize(query)>. */
 int v3d_ground_scores(const void* obj, int64_t ldo, int n_rows, const void* query, int C, void* scores, int dtype,
                       void* stream);
+
+/* The same scores for G queries in one launch (one scene's proposals against a batch of grounding queries):
+ * scores[g * lds + i] = <normalize(obj[i]), normalize(queries + g * ldq)>, i < n_rows, g < G; grid (n_rows, G).  Every (object, query)
+ * pair goes through v3d_ground_scores' own arithmetic, so row g equals v3d_ground_scores(obj, ..., queries + g * ldq, ...) bit for
+ * bit.  f16 / bf16, any C > 0, ldo, ldq >= C, lds >= n_rows. */
+int v3d_ground_scores_rows(const void* obj, int64_t ldo, int n_rows, const void* queries, int64_t ldq, int G, int C, void* scores,
+                           int64_t lds, int dtype, void* stream);
 
 /* ------------------------------------------------------------------ data movement ------- */
 

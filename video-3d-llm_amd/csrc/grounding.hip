@@ -109,6 +109,36 @@ __global__ __launch_bounds__(256) void ground_scores_kernel(const T* __restrict_
   if (tid == 0) scores[i] = from_f32<T>(red[2][0] + red[2][1] + red[2][2] + red[2][3]);
 }
 
+// ground_scores_kernel for G queries in one launch (one scene prefill, many grounding queries): block (i, g) scores object row i
+// against query row g with ground_scores_kernel's own arithmetic - the same strided f32 sums and wave / LDS fold, the norms rounded to
+// T, each normalised element rounded, each product rounded - so row g of the result carries the bits of the one-query launch.
+template <typename T>
+__global__ __launch_bounds__(256) void ground_scores_rows_kernel(const T* __restrict__ obj, int64_t ldo, const T* __restrict__ queries,
+                                                                 int64_t ldq, int C, T* __restrict__ scores, int64_t lds) {
+  __shared__ float red[3][4];
+  const int i = blockIdx.x, g = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const T* row = obj + (size_t)i * ldo;
+  const T* q = queries + (size_t)g * ldq;
+  float so = 0.f, sq = 0.f;
+  for (int c = tid; c < C; c += 256) {
+    const float a = to_f32(row[c]), b = to_f32(q[c]);
+    so = fmaf(a, a, so); sq = fmaf(b, b, sq);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { so += __shfl_xor(so, off); sq += __shfl_xor(sq, off); }
+  if (lane == 0) { red[0][wave] = so; red[1][wave] = sq; }
+  __syncthreads();
+  const float no = fmaxf(round_to<T>(sqrtf(red[0][0] + red[0][1] + red[0][2] + red[0][3])), 1e-12f);
+  const float nq = fmaxf(round_to<T>(sqrtf(red[1][0] + red[1][1] + red[1][2] + red[1][3])), 1e-12f);
+  float dot = 0.f;
+  for (int c = tid; c < C; c += 256) dot += round_to<T>(round_to<T>(to_f32(row[c]) / no) * round_to<T>(to_f32(q[c]) / nq));
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) dot += __shfl_xor(dot, off);
+  if (lane == 0) red[2][wave] = dot;
+  __syncthreads();
+  if (tid == 0) scores[(size_t)g * lds + i] = from_f32<T>(red[2][0] + red[2][1] + red[2][2] + red[2][3]);
+}
+
 
 // The 'mlp' and 'score' grounding heads (llava_qwen.py:59-86, 283-293) beside the shipped 'infonce' one - small row work:
 //   row_dots:       out[i] = sum_c x[i, c] * q[c] (+ bias).  PRODUCTS_ROUNDED: `(ground_hidden * object_features).sum(-1)` of the 'mlp'
@@ -185,6 +215,17 @@ extern "C" int v3d_ground_scores(const void* obj, int64_t ldo, int n_rows, const
   else if (dtype == V3D_F16) hipLaunchKernelGGL(ground_scores_kernel<f16_t>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, (const f16_t*)obj, ldo, (const f16_t*)query, C, (f16_t*)scores);
   else { set_error("v3d_ground_scores: dtype must be f16 or bf16"); return V3D_E_INVALID; }
   return check_launch("v3d_ground_scores");
+}
+
+extern "C" int v3d_ground_scores_rows(const void* obj, int64_t ldo, int n_rows, const void* queries, int64_t ldq, int G, int C,
+                                      void* scores, int64_t lds, int dtype, void* stream) {
+  V3D_REQUIRE(obj && queries && scores && n_rows > 0 && G > 0 && G <= 65535 && C > 0 && ldo >= C && ldq >= C && lds >= n_rows,
+              "v3d_ground_scores_rows: bad arguments");
+  const dim3 grid(n_rows, G);
+  if (dtype == V3D_BF16) hipLaunchKernelGGL(ground_scores_rows_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)obj, ldo, (const bf16_t*)queries, ldq, C, (bf16_t*)scores, lds);
+  else if (dtype == V3D_F16) hipLaunchKernelGGL(ground_scores_rows_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const f16_t*)obj, ldo, (const f16_t*)queries, ldq, C, (f16_t*)scores, lds);
+  else { set_error("v3d_ground_scores_rows: dtype must be f16 or bf16"); return V3D_E_INVALID; }
+  return check_launch("v3d_ground_scores_rows");
 }
 
 extern "C" int v3d_row_dots(const void* x, int64_t ldx, int n_rows, const void* q, int C, const void* bias, int products_rounded,

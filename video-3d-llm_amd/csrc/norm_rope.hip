@@ -227,6 +227,25 @@ __global__ __launch_bounds__(256) void add_row_kernel(T* __restrict__ x, int64_t
   }
 }
 
+// x[rows[i], :C] = T(x[rows[i], :C] + add[src[i], :C]) - add_row with a source row per destination row (the box-centre PEs of a batch of
+// Scan2Cap questions on their <coord> rows).  rows must be distinct (two blocks would race on one row); src may repeat.
+// nv: 16-byte vectors per row (C / 8 where the strides and bases allow them, else 0); the columns past 8 * nv go one by one.
+template <typename T>
+__global__ __launch_bounds__(256) void add_rows_kernel(T* __restrict__ x, int64_t ldx, const int64_t* __restrict__ rows,
+                                                       const int64_t* __restrict__ src, int C, int nv, const T* __restrict__ add,
+                                                       int64_t lda) {
+  T* r = x + rows[blockIdx.x] * ldx;
+  const T* a_row = add + src[blockIdx.x] * lda;
+  for (int k = threadIdx.x; k < nv; k += blockDim.x) {
+    const uint4 a = reinterpret_cast<const uint4*>(r)[k], b = reinterpret_cast<const uint4*>(a_row)[k];
+    float o[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = vec_get<T>(a, j) + vec_get<T>(b, j);
+    reinterpret_cast<uint4*>(r)[k] = vec_pack<T>(o);
+  }
+  for (int c = nv * 8 + threadIdx.x; c < C; c += blockDim.x) r[c] = from_f32<T>(to_f32(r[c]) + to_f32(a_row[c]));
+}
+
 // strided row copy (KV-cache append, im2col-free patch gather, ...): out[r, :cols] = in[r, :cols]
 template <typename T>
 __global__ __launch_bounds__(256) void copy_rows_kernel(const T* __restrict__ in, int64_t ldi, T* __restrict__ out,
@@ -405,6 +424,16 @@ extern "C" int v3d_add_row(void* x, int64_t ldx, const int64_t* rows, int n_rows
   V3D_DISPATCH_16(dtype, hipLaunchKernelGGL(add_row_kernel<T>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, (T*)x, ldx, rows, C,
                                             (const T*)add));
   return check_launch("v3d_add_row");
+}
+
+extern "C" int v3d_add_rows(void* x, int64_t ldx, const int64_t* rows, const int64_t* src, int n_rows, int C, const void* add, int64_t lda,
+                            int dtype, void* stream) {
+  V3D_REQUIRE(x && rows && src && add && n_rows >= 0 && C > 0 && ldx >= C && lda >= C, "v3d_add_rows: bad arguments");
+  if (n_rows == 0) return V3D_OK;
+  const int nv = (ldx % 8 == 0 && lda % 8 == 0 && aligned16(x) && aligned16(add)) ? C / 8 : 0;
+  V3D_DISPATCH_16(dtype, hipLaunchKernelGGL(add_rows_kernel<T>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, (T*)x, ldx, rows, src, C, nv,
+                                            (const T*)add, lda));
+  return check_launch("v3d_add_rows");
 }
 
 extern "C" int v3d_copy_rows(const void* in, int64_t ldi, void* out, int64_t ldo, int64_t rows, int cols, int dtype, void* stream) {

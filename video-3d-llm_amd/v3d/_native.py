@@ -87,10 +87,12 @@ SIGNATURES = {
     "v3d_object_patch_mask": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p]),
     "v3d_masked_mean": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p]),
     "v3d_ground_scores": (c_i, [c_p, c_l, c_i, c_p, c_i, c_p, c_i, c_p]),
+    "v3d_ground_scores_rows": (c_i, [c_p, c_l, c_i, c_p, c_l, c_i, c_i, c_p, c_l, c_i, c_p]),
     "v3d_row_dots": (c_i, [c_p, c_l, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p]),
     "v3d_relu_mul_rows": (c_i, [c_p, c_l, c_i, c_i, c_p, c_i, c_i, c_p]),
     "v3d_rope_kv_store": (c_i, [c_p, c_l, c_l, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_l, c_p, c_l, c_i, c_p]),
     "v3d_add_row": (c_i, [c_p, c_l, c_p, c_i, c_i, c_p, c_i, c_p]),
+    "v3d_add_rows": (c_i, [c_p, c_l, c_p, c_p, c_i, c_i, c_p, c_l, c_i, c_p]),
     "v3d_copy_rows_bcast": (c_i, [c_p, c_l, c_p, c_l, c_l, c_i, c_i, c_l, c_i, c_p]),
     "v3d_copy_rows": (c_i, [c_p, c_l, c_p, c_l, c_l, c_i, c_i, c_p]),
     "v3d_patchify": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),

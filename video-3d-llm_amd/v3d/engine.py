@@ -675,16 +675,7 @@ class Engine:
         'infonce' (llava_qwen.py:87-104, 294-300) cosine of two MLPs, zero-target appended; 'mlp' (:59-71, 283-285) one MLP on the
         query, product-and-sum with the raw object features; 'score' (:72-86, 286-292) two MLPs, their product, a scoring MLP."""
         g, kind = self.ground, self.cfg.ground_head_type
-
-        def relu_ln(xin, pfx):                       # Linear, ReLU, LayerNorm, Linear
-            h = ops.gemm(xin, g[pfx + "0.weight"], bias=g[pfx + "0.bias"], epilogue=ops.EPI_BIAS_RELU)
-            hn = ops.layernorm(h, g[pfx + "2.weight"], g[pfx + "2.bias"], 1e-5)
-            return ops.gemm(hn, g[pfx + "3.weight"], bias=g[pfx + "3.bias"], epilogue=ops.EPI_BIAS)
-
-        def ln_relu(xin, pfx, last=True):            # Linear, LayerNorm, ReLU (, Linear)
-            h = ops.gemm(xin, g[pfx + "0.weight"], bias=g[pfx + "0.bias"], epilogue=ops.EPI_BIAS)
-            hn = ops.relu_mul_rows(ops.layernorm(h, g[pfx + "1.weight"], g[pfx + "1.bias"], 1e-5))
-            return ops.gemm(hn, g[pfx + "3.weight"], bias=g[pfx + "3.bias"], epilogue=ops.EPI_BIAS) if last else hn
+        relu_ln, ln_relu = self._relu_ln, self._ln_relu
 
         if kind == "infonce":
             of = torch.cat([object_features, g["ground_head_zero_target"][None]], 0).contiguous()
@@ -696,6 +687,20 @@ class Engine:
         mul = ops.relu_mul_rows(obj, row=qf[0].contiguous(), relu=False)                      # obj_feat * query_feat
         hn = ln_relu(mul, "ground_head_score.", last=False)
         return ops.row_dots(hn, g["ground_head_score.3.weight"][0].contiguous(), bias=g["ground_head_score.3.bias"])
+
+    def _relu_ln(self, xin, pfx):
+        """Linear, ReLU, LayerNorm, Linear of the grounding head's weights under `pfx`"""
+        g = self.ground
+        h = ops.gemm(xin, g[pfx + "0.weight"], bias=g[pfx + "0.bias"], epilogue=ops.EPI_BIAS_RELU)
+        hn = ops.layernorm(h, g[pfx + "2.weight"], g[pfx + "2.bias"], 1e-5)
+        return ops.gemm(hn, g[pfx + "3.weight"], bias=g[pfx + "3.bias"], epilogue=ops.EPI_BIAS)
+
+    def _ln_relu(self, xin, pfx, last=True):
+        """Linear, LayerNorm, ReLU (, Linear)"""
+        g = self.ground
+        h = ops.gemm(xin, g[pfx + "0.weight"], bias=g[pfx + "0.bias"], epilogue=ops.EPI_BIAS)
+        hn = ops.relu_mul_rows(ops.layernorm(h, g[pfx + "1.weight"], g[pfx + "1.bias"], 1e-5))
+        return ops.gemm(hn, g[pfx + "3.weight"], bias=g[pfx + "3.bias"], epilogue=ops.EPI_BIAS) if last else hn
 
     def object_features(self, feats, coords, boxes):
         """Object-proposal features (llava_arch.py:351-376, 479-501): per box, the mean of the rows whose image cell has enough of
@@ -730,18 +735,32 @@ class Engine:
 
     # ------------------------------------------------------------------ scene-level reuse
     @torch.no_grad()
-    def prefill_scene(self, prefix_ids, images, world_coords):
+    def prefill_scene(self, prefix_ids, images, world_coords, objects=None):
         """Everything of a (scene, question) pass that does not depend on the question, done once per scene: ViT + projector,
         voxel ids, the visual tokens and the decoder over the prompt prefix [system | user | <image>] - the reference's eval loop
         recomputes all of it for every question of a scene (model_scanqa.py:130-185; the prefix is question-independent,
         :46-60).  prefix_ids: the prompt ids up to and INCLUDING the <image> placeholder (-200) (further question-independent
         ids may follow it).  The K/V rows of the prefix stay in the current context's cache; returns the prefix length P.
-        Follow with answer(question_ids) any number of times."""
+        Follow with answer(question_ids) any number of times.
+        objects [n, 6] (the scene's box proposals; ScanRefer / Multi3DRefer): the object features (object_features) and, for the
+        'infonce' head, its object branch over [features | zero-target] are computed as well and kept on the context (ctx.ground_of
+        [n, H], ctx.ground_obj [n + 1, C]) - the context's own tensors, since another scene may be prefilled through the shared
+        workspaces before this one's queries run.  Follow with ground_group(questions, ground_rows)."""
+        if objects is not None and self.ground is None:
+            raise V3DError("this engine was built without ground_head_* weights")
         feats = self.encode_images(images)
-        ids = self.voxel_ids(world_coords.to(self.dtype))
+        coords = world_coords.to(self.dtype)
+        ids = self.voxel_ids(coords)
         x = self.build_inputs_embeds(prefix_ids, feats, ids)
         self.llm_forward(x, 0, head=False, last_rows=[])          # the prefix only leaves its K/V rows behind
         self.ctx.prefix_len = x.shape[0]
+        self.ctx.ground_of = self.ctx.ground_obj = None
+        if objects is not None:
+            of = self.object_features(feats, coords, objects.to(device=self.device, dtype=self.dtype).contiguous())
+            self.ctx.ground_of = of
+            if self.cfg.ground_head_type == "infonce":
+                zt = self.ground["ground_head_zero_target"][None]
+                self.ctx.ground_obj = self._relu_ln(torch.cat([of, zt], 0).contiguous(), "ground_head_obj.")
         return self.ctx.prefix_len
 
     @torch.no_grad()
@@ -786,22 +805,59 @@ class Engine:
             raise V3DError(f"answer_group takes 1 to {st.n} questions")
         return st
 
-    @torch.no_grad()
-    def answer_group(self, questions, max_new_tokens=16, eos_token_id=None):
-        """Up to 32 questions about the scene prefilled by prefill_scene, answered together: the cached prefix K/V is handed to
-        each question's own cache (one broadcast copy per layer), the questions' rows run through the decoder as ONE batch
-        (one pass over the weights; rows padded to the longest question, which causality keeps from affecting the real rows),
-        then all answers decode as one group (decode_group).  Returns a list of token-id tensors, each cut after its first EOS.
-        A question's rows do not depend on the others (tests/test_gpu_scene_reuse.py: equal to answer() on it alone)."""
+    def question_embeds(self, questions, box_inputs=None, coord_token_id=None):
+        """The embedding rows of up to 32 questions as answer_group / ground_group batch them: [G * Sq, hidden] (a view of the
+        batch's residual stream), question g in rows g * Sq .., padded to the longest with copies of its last id.
+        box_inputs[g] = [x, y, z] or None, with coord_token_id (Scan2Cap): the PE of question g's discretised box centre is added to
+        the rows of its <coord> tokens, as build_inputs_embeds does for one prompt (llava_arch.py:416-417, 697-700) - every centre
+        through ONE discrete_coords + sin3d_pe call, every row through ONE add_rows launch; pad rows never take a PE."""
+        G = len(questions)
+        if not 1 <= G <= self.MAX_GROUP:
+            raise V3DError(f"a group holds 1 to {self.MAX_GROUP} questions")
+        st = self._answer_state(G)
+        host = [q.cpu() for q in questions]
+        lens = [int(q.numel()) for q in host]
+        if min(lens) < 1:
+            raise V3DError(f"a group holds 1 to {self.MAX_GROUP} non-empty questions")
+        Sq = max(lens)
+        if G * Sq > self.cfg.llm.max_pos:
+            raise V3DError(f"{G} questions x {Sq} rows exceed the engine's {self.cfg.llm.max_pos}-row workspaces")
+        if box_inputs is not None and len(box_inputs) != G:
+            raise V3DError("box_inputs: one entry ([x, y, z] or None) per question")
+        ids = torch.empty((G, Sq), dtype=torch.int64)
+        for g, q in enumerate(host):
+            ids[g, : lens[g]] = q
+            ids[g, lens[g]:] = q[-1]                        # pad rows: any valid id; they sit AFTER the real rows (causal)
+        x = ops.embed_gather(self.embed, ids.reshape(-1).to(self.device), out=st.x[: G * Sq])
+        if box_inputs is not None and coord_token_id is not None:
+            rows, src, centres = [], [], []
+            for g, (q, box) in enumerate(zip(host, box_inputs)):
+                hit = [] if box is None else [g * Sq + j for j, t in enumerate(q.tolist()) if t == coord_token_id]
+                if hit:
+                    rows += hit
+                    src += [len(centres)] * len(hit)
+                    centres.append([float(v) for v in torch.as_tensor(box, dtype=torch.float32).reshape(-1)[:3]])
+            if rows:
+                c = self.cfg
+                centre = ops.discrete_coords(torch.tensor(centres, dtype=torch.float32).to(device=self.device, dtype=self.dtype),
+                                             c.min_xyz, c.max_xyz, c.voxel_size)
+                pe = ops.sin3d_pe(centre[None], c.llm.hidden, dim_t=self.pe_table.dim_t)[0]
+                ops.add_rows(x, rows, src, pe)
+        return x
+
+    def _question_rows(self, what, questions, max_new_tokens, box_inputs=None, coord_token_id=None):
+        """The part answer_group and ground_group share: the questions' rows (question_embeds) through the decoder as ONE batch behind
+        the prefix prefill_scene left in the current context.  -> (scene, st, x, P, lens, Sq, share): x [G * Sq, hidden] is the
+        residual stream after the last layer (before the final norm), question g in rows g * Sq .. g * Sq + lens[g]."""
         scene = self.ctx
         P = getattr(scene, "prefix_len", 0)
         if not P or scene.kv_len < P:
-            raise V3DError("answer_group() needs prefill_scene() on this context first")
+            raise V3DError(f"{what}() needs prefill_scene() on this context first")
         G = len(questions)
         st = self._answer_state(G)
         lens = [int(q.numel()) for q in questions]
         if G < 1 or min(lens) < 1:
-            raise V3DError(f"answer_group() needs 1 to {self.MAX_GROUP} non-empty questions")
+            raise V3DError(f"{what}() needs 1 to {self.MAX_GROUP} non-empty questions")
         Sq = max(lens)
         l = self.cfg.llm
         if G * Sq > l.max_pos:
@@ -818,11 +874,7 @@ class Engine:
                 ops.copy_rows_bcast(scene.kv[i][:P], st.kv[i][:G])
             elif P > P0:
                 ops.copy_rows_bcast(scene.kv[i][P0:P], st.kv[i][:G, P0:])
-        ids = torch.empty((G, Sq), dtype=torch.int64)
-        for g, q in enumerate(questions):
-            ids[g, : lens[g]] = q.cpu()
-            ids[g, lens[g]:] = q[-1]                        # pad rows: any valid id; they sit AFTER the real rows (causal)
-        x = ops.embed_gather(self.embed, ids.reshape(-1).to(self.device), out=st.x[: G * Sq])
+        x = self.question_embeds(questions, box_inputs, coord_token_id)
         b = SceneContext()
         b.B, b.Sq, b.kv = G, Sq, st.kv
         j = torch.arange(Sq)
@@ -831,6 +883,18 @@ class Engine:
         if share:
             b.shared_kv, b.shared_len = scene.kv, P0
         self.llm_forward(x, P, head=False, batch=b)
+        return scene, st, x, P, lens, Sq, share
+
+    @torch.no_grad()
+    def answer_group(self, questions, max_new_tokens=16, eos_token_id=None, box_inputs=None, coord_token_id=None):
+        """Up to 32 questions about the scene prefilled by prefill_scene, answered together: the cached prefix K/V is handed to
+        each question's own cache (one broadcast copy per layer), the questions' rows run through the decoder as ONE batch
+        (one pass over the weights; rows padded to the longest question, which causality keeps from affecting the real rows),
+        then all answers decode as one group (decode_group).  Returns a list of token-id tensors, each cut after its first EOS.
+        A question's rows do not depend on the others (tests/test_gpu_scene_reuse.py: equal to answer() on it alone).
+        box_inputs / coord_token_id (Scan2Cap): question_embeds - each question's box-centre PE on its <coord> rows."""
+        scene, st, x, P, lens, Sq, share = self._question_rows("answer_group", questions, max_new_tokens, box_inputs, coord_token_id)
+        G, l = len(questions), self.cfg.llm
         last = torch.tensor([g * Sq + lens[g] - 1 for g in range(G)], dtype=torch.int64, device=self.device)
         rows = st.rows
         ops.embed_gather(x, last, out=rows.x[:G])                                     # each question's last real row
@@ -846,6 +910,34 @@ class Engine:
                                  eos_token_id=eos_token_id, prefix_kv=scene.kv if share else None)
         self.use(scene)
         return [r.to(self.device) for r in self.trim_at_eos(toks, eos_token_id)]
+
+    @torch.no_grad()
+    def ground_group(self, questions, ground_rows):
+        """Up to 32 grounding queries about the scene prefilled by prefill_scene(..., objects=...): the queries' rows (the ids that
+        follow the prefix in the full prompt, the assistant turn with its <ground> label included) run through the decoder as ONE
+        batch over the cached prefix, as answer_group's do; ground_rows[g] is the index INSIDE question g of the <ground> label token.
+        Its residual row goes through the final RMSNorm and the query branch of the grounding head ([G, H] at once), and - 'infonce' -
+        one ground_scores_rows launch scores every query against the scene's object branch: scores [G, n + 1] (the last column = the
+        zero-target).  'mlp' / 'score': the one-query head per row, [G, n].  The reference runs the whole prompt, ViT included, per
+        query (model_scanrefer.py:165-173)."""
+        if self.ground is None:
+            raise V3DError("this engine was built without ground_head_* weights")
+        G = len(questions)
+        if not 1 <= G <= self.MAX_GROUP:
+            raise V3DError(f"ground_group takes 1 to {self.MAX_GROUP} queries")
+        P = getattr(self.ctx, "prefix_len", 0)
+        if P and self.ctx.kv_len >= P and getattr(self.ctx, "ground_of", None) is None:
+            raise V3DError("ground_group() needs a scene prefilled WITH its objects: prefill_scene(..., objects=...)")
+        if len(ground_rows) != G or any(not 0 <= int(r) < int(q.numel()) for q, r in zip(questions, ground_rows)):
+            raise V3DError("ground_group: ground_rows[g] must index a row of question g")
+        scene, st, x, P, lens, Sq, share = self._question_rows("ground_group", questions, 1)
+        sel = torch.tensor([g * Sq + int(r) for g, r in enumerate(ground_rows)], dtype=torch.int64).to(self.device)
+        rows = st.rows
+        ops.embed_gather(x, sel, out=rows.x[:G])                                      # each query's <ground> row (never a pad row)
+        query = ops.rmsnorm(rows.x[:G], self.l_norm, self.cfg.llm.eps, out=rows.last[:G])
+        if self.cfg.ground_head_type == "infonce":
+            return ops.ground_scores_rows(scene.ground_obj, self._relu_ln(query, "ground_head_query."))
+        return torch.stack([self.ground_head(query[g: g + 1], scene.ground_of) for g in range(G)])
 
     @torch.no_grad()
     def generate_group(self, samples, max_new_tokens=16, eos_token_id=None):

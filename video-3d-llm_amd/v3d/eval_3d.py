@@ -15,6 +15,14 @@ loader, one gather to rank 0 that writes the JSONL in question order):
   multi3drefer  llava/eval/model_multi3drefer.py:120-185      the same forward                                  "scores" + "objects" (:171-181)
   scanqa        llava/eval/model_scanqa.py                    = v3d.eval_scanqa
 
+--reuse-scenes (every task; not a reference mode): consecutive lines of one scene share ONE scene prefill (Engine.prefill_scene) and run
+in batches of up to 32 over its cached prefix, pipelined (v3d.pipeline.SceneReusePipeline) or, with --no-pipeline, one scene after the other:
+  scanqa, sqa3d             Engine.answer_group
+  scan2cap                  Engine.answer_group with each line's box centre: its PE goes on that line's <coord> rows inside the batch
+  scanrefer, multi3drefer   the scene's proposals go into the prefill (object features + the head's object branch, once per scene);
+                            Engine.ground_group scores a batch of queries against them
+The records keep their keys and order; sharding defaults to whole scenes per rank.
+
 `v3d.eval_ground`, `v3d.eval_scan2cap`, `v3d.eval_sqa3d` are entry points with the task fixed.
 """
 import argparse
@@ -83,14 +91,34 @@ def ground_record(task, line, scores, objects_half, model_name, extra_prompt=E.E
 
 
 def ground_answer_fn(task, model, tokenizer, image_processor, video_processor, model_name, max_frame_num=32, workers=None, pool=None,
-                     stats=None, sync_every=16):
+                     stats=None, sync_every=16, reuse_scenes=False, pipeline=True):
     """Per-rank loop of the grounding drivers around the engine: host loader -> device inputs -> ONE prefill with the object proposals
     (Engine.ground_scores: patch masks + masked means + box-centre PE, decoder, infonce head) -> scores.  The scores stay on the
-    device and are fetched every `sync_every` questions, so the launch queue does not drain per question."""
-    from .pipeline import AsyncSceneLoader, ScenePipeline, SceneSample
+    device and are fetched every `sync_every` questions, so the launch queue does not drain per question.
+    reuse_scenes: consecutive lines of one scene share ONE prefill of [system | user | <image>] with the scene's proposals
+    (Engine.prefill_scene(objects=...)); their remaining rows run in batches of up to 32 (Engine.ground_group), scores fetched per
+    batch - on v3d.pipeline.SceneReusePipeline (pipeline=True: the next scene's prefill beside this scene's batches) or one scene after
+    the other on one stream; both give the same records."""
+    from .pipeline import AsyncSceneLoader, SceneJob, ScenePipeline, SceneReusePipeline, SceneSample
     gt_ids = getattr(model.config, "ground_token_ids", None)
     if not gt_ids:
         raise ValueError("config.ground_token_ids is needed to locate the <ground> label (train_3d.py:1698-1713 stores it)")
+
+    def prompt(line):
+        """-> (ids [S], index of the <ground> label token in ids)"""
+        ids, labels = chatml_ids_labels([line["conversations"][0], line["conversations"][1]], tokenizer)
+        if int((ids == IMAGE_TOKEN_INDEX).sum()) != 1:
+            raise ValueError("exactly one <image> placeholder per prompt")
+        loc = ((labels[0] >= gt_ids[0]) & (labels[0] <= gt_ids[-1])).nonzero().flatten()
+        if loc.numel() != 1:
+            raise ValueError("exactly one <ground> label token expected (llava_qwen.py:280-281)")
+        return ids[0], int(loc[0])
+
+    def describe(vid):
+        return video_processor.describe_scene(vid, True, max_frame_num)
+
+    def n_workers():
+        return E.default_workers() if workers is None else workers
 
     def run(lines):
         eng = model.engine
@@ -99,8 +127,7 @@ def ground_answer_fn(task, model, tokenizer, image_processor, video_processor, m
             pipe = model.__dict__["_v3d_pipeline"] = ScenePipeline(
                 eng, 16, crop=image_processor.crop_size["width"], image_mean=image_processor.image_mean,
                 image_std=image_processor.image_std, rescale=image_processor.rescale_factor, prefill_streams=2)
-        loader = AsyncSceneLoader([l["video"] for l in lines], lambda vid: video_processor.describe_scene(vid, True, max_frame_num),
-                                  workers=E.default_workers() if workers is None else workers, pool=pool)
+        loader = AsyncSceneLoader([l["video"] for l in lines], describe, workers=n_workers(), pool=pool)
         out, pending = [], []
         t0 = time.time()
 
@@ -112,16 +139,11 @@ def ground_answer_fn(task, model, tokenizer, image_processor, video_processor, m
         try:
             with torch.inference_mode():
                 for j, line in enumerate(lines):
-                    ids, labels = chatml_ids_labels([line["conversations"][0], line["conversations"][1]], tokenizer)
-                    if int((ids == IMAGE_TOKEN_INDEX).sum()) != 1:
-                        raise ValueError("exactly one <image> placeholder per prompt")
-                    loc = ((labels[0] >= gt_ids[0]) & (labels[0] <= gt_ids[-1])).nonzero().flatten()
-                    if loc.numel() != 1:
-                        raise ValueError("exactly one <ground> label token expected (llava_qwen.py:280-281)")
+                    ids, loc = prompt(line)
                     raw, _ = loader.get(j)
-                    images, coords = pipe.device_inputs(SceneSample(input_ids=ids[0], raw=raw, key=line["video"]))
+                    images, coords = pipe.device_inputs(SceneSample(input_ids=ids, raw=raw, key=line["video"]))
                     objects = torch.tensor(video_processor.scan2obj[line["video"]]).to(torch.float16)       # the driver's .half()
-                    scores = eng.ground_scores(ids[0], int(loc[0]), images, coords, objects.to(eng.device))
+                    scores = eng.ground_scores(ids, loc, images, coords, objects.to(eng.device))
                     pending.append((line, scores, objects))
                     if len(pending) >= sync_every:
                         flush()
@@ -132,20 +154,68 @@ def ground_answer_fn(task, model, tokenizer, image_processor, video_processor, m
             stats.update({"host_thread_seconds": dict(loader.stage_seconds), "questions": len(lines), "wall_seconds": time.time() - t0})
         return out
 
-    return run
+    def run_reuse(lines):
+        if not lines:
+            return []
+        eng = model.engine
+        pipe = model.__dict__.get("_v3d_reuse_pipeline")
+        if pipe is None:
+            pipe = model.__dict__["_v3d_reuse_pipeline"] = SceneReusePipeline(
+                eng, crop=image_processor.crop_size["width"], image_mean=image_processor.image_mean, image_std=image_processor.image_std,
+                rescale=image_processor.rescale_factor)
+        groups, i = [], 0                                  # runs of consecutive lines about one scene
+        while i < len(lines):
+            j = i
+            while j < len(lines) and lines[j]["video"] == lines[i]["video"]:
+                j += 1
+            prompts = [prompt(l) for l in lines[i:j]]
+            at = int((prompts[0][0] == IMAGE_TOKEN_INDEX).nonzero()[0])
+            prefix = prompts[0][0][: at + 1]
+            if any(not torch.equal(ids[: at + 1], prefix) for ids, _ in prompts):
+                raise ValueError("queries of one scene must share the prompt prefix up to <image>")
+            if any(loc <= at for _, loc in prompts):
+                raise ValueError("the <ground> label must follow the <image> placeholder")
+            objects = torch.tensor(video_processor.scan2obj[lines[i]["video"]]).to(torch.float16)           # the driver's .half()
+            groups.append((lines[i]["video"], prefix, objects,
+                           SceneJob(questions=[ids[at + 1:] for ids, _ in prompts], objects=objects,
+                                    ground_rows=[loc - at - 1 for _, loc in prompts])))
+            i = j
+        loader = AsyncSceneLoader([g[0] for g in groups], describe, workers=n_workers(), pool=pool, ahead=2, keep=2)
+        t0 = time.time()
+        try:
+            with torch.inference_mode():
+                if pipeline:
+                    def scenes():
+                        for k, (vid, prefix, _, job) in enumerate(groups):
+                            yield SceneSample(input_ids=prefix, raw=loader.get(k)[0], key=None), job
+                    scores = pipe.run(scenes(), 1)
+                else:
+                    scores, nb = [], eng.MAX_GROUP
+                    for k, (vid, prefix, objects, job) in enumerate(groups):
+                        images, coords = pipe.inputs.device_inputs(SceneSample(input_ids=prefix, raw=loader.get(k)[0], key=None))
+                        eng.prefill_scene(prefix, images, coords, objects=objects)
+                        scores.append([sc for b in range(0, len(job.questions), nb)
+                                       for sc in eng.ground_group(job.questions[b: b + nb], job.ground_rows[b: b + nb]).cpu()])
+        finally:
+            loader.close()
+        if stats is not None:
+            stats.update({"host_thread_seconds": dict(loader.stage_seconds), "questions": len(lines), "scenes": len(groups),
+                          "wall_seconds": time.time() - t0})
+        flat = [(sc, g[2]) for g, per_scene in zip(groups, scores) for sc in per_scene]
+        return [ground_record(task, line, sc, obj, model_name) for line, (sc, obj) in zip(lines, flat)]
+
+    return run_reuse if reuse_scenes else run
 
 
 def answer_fn_for(task, model, tokenizer, image_processor, video_processor, model_name, a, pool=None, times=None, stats=None):
     if task in GROUND_TASKS:
         return ground_answer_fn(task, model, tokenizer, image_processor, video_processor, model_name, a.max_frame_num,
-                                workers=(0 if a.loader_workers < 0 else a.loader_workers or None), pool=pool, stats=stats)
+                                workers=(0 if a.loader_workers < 0 else a.loader_workers or None), pool=pool, stats=stats,
+                                reuse_scenes=a.reuse_scenes, pipeline=not a.no_pipeline)
     kw = dict(max_frame_num=a.max_frame_num, max_new_tokens=a.max_new_tokens, reuse_scenes=a.reuse_scenes, times=times,
               pipeline=not a.no_pipeline, group_size=a.decode_group, workers=(0 if a.loader_workers < 0 else a.loader_workers or None),
               pool=pool, stats=stats)
     if task == "scan2cap":                      # model_scan2cap.py:137-139, 199-212
-        if a.reuse_scenes:
-            raise NotImplementedError("--reuse-scenes: the Scan2Cap prompt's <coord> rows differ per question inside the prefix's reach")
-
         def record(line, text):
             r = E.make_record(line, text, model_name)
             r["gt_response"] = line.get("annotations", [line["conversations"][1]["value"]])

@@ -207,8 +207,17 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
             return out
         return with_skipped(lines, run)
 
+    def _boxes(lines):
+        """(box_inputs, coord_token_id) of answer_group for these lines: None, None unless the task has box inputs (Scan2Cap)"""
+        if box_input_fn is None or not coord_ids:
+            return None, None
+        return [box_input_fn(l) for l in lines], coord_ids[0]
+
     def scene_batches(lines):
         """Consecutive questions of one scene: ONE scene prefill, answers in batches of up to 32 (Engine.answer_group)."""
+        return with_skipped(lines, _scene_batch_texts)
+
+    def _scene_batch_texts(lines):
         eng, out, i = model.engine, [], 0
         nb = eng.MAX_GROUP
         eos = model._eos()
@@ -227,8 +236,10 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
                 for b in range(i, j, nb):
                     qs = [x[at + 1:] for x in ids[b - i: min(j, b + nb) - i]]
                     room = eng.cfg.llm.max_pos - P - max(len(q) for q in qs) + 1
-                    answers = eng.answer_group(qs, max_new_tokens=min(max_new_tokens, room), eos_token_id=eos)
-                    out += [record_fn(l, decode(a)) for l, a in zip(lines[b: b + len(qs)], answers)]
+                    boxes, coord_id = _boxes(lines[b: b + len(qs)])
+                    answers = eng.answer_group(qs, max_new_tokens=min(max_new_tokens, room), eos_token_id=eos, box_inputs=boxes,
+                                               coord_token_id=coord_id)
+                    out += [decode(a) for a in answers]
             i = j
         return out
 
@@ -285,7 +296,7 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
         return with_skipped(lines, _scene_pipelined_texts)
 
     def _scene_pipelined_texts(lines):
-        from .pipeline import AsyncSceneLoader, SceneReusePipeline, SceneSample
+        from .pipeline import AsyncSceneLoader, SceneJob, SceneReusePipeline, SceneSample
         if not lines:
             return []
         eng = model.engine
@@ -306,7 +317,8 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
             prefix = ids[0][: at + 1]
             if any(not torch.equal(x[: at + 1], prefix) for x in ids):
                 raise ValueError("questions of one scene must share the prompt prefix up to <image>")
-            groups.append((lines[i]["video"], prefix, [x[at + 1:] for x in ids]))
+            boxes, coord_id = _boxes(lines[i:j])
+            groups.append((lines[i]["video"], prefix, SceneJob(questions=[x[at + 1:] for x in ids], box_inputs=boxes, coord_token_id=coord_id)))
             i = j
         loader = AsyncSceneLoader([g[0] for g in groups], lambda vid: video_processor.describe_scene(vid, True, max_frame_num),
                                   workers=default_workers() if workers is None else workers, pool=pool, ahead=2, keep=2)

@@ -531,6 +531,31 @@ def add_row(x, rows, add):
     return x
 
 
+def add_rows(x, rows, src, add):
+    """x[rows[i]] += add[src[i]] in ONE launch (rows, src: equally long host lists or int64 tensors; add [m, C] of x's dtype): the
+    box-centre PEs of a batch of questions on their <coord> rows.  `rows` must be distinct - two workgroups adding into one row would
+    race - which is checked here while the list is on the host (a device tensor is taken as given); `src` may repeat."""
+    if x.dim() != 2 or add.dim() != 2 or add.dtype != x.dtype or add.shape[1] != x.shape[1] or x.stride(1) != 1 or add.stride(1) != 1:
+        raise V3DError(f"add_rows: add {tuple(add.shape)} {add.dtype} against x {tuple(x.shape)} {x.dtype}")
+    if not (torch.is_tensor(rows) and rows.is_cuda):
+        host = [int(r) for r in (rows.tolist() if torch.is_tensor(rows) else rows)]
+        if len(set(host)) != len(host):
+            raise V3DError("add_rows: destination rows must be distinct")
+        if host and not (0 <= min(host) and max(host) < x.shape[0]):
+            raise V3DError(f"add_rows: rows outside x ({x.shape[0]} rows)")
+        rows = torch.tensor(host, dtype=torch.int64).to(x.device, non_blocking=True)
+    if not (torch.is_tensor(src) and src.is_cuda):
+        host = [int(r) for r in (src.tolist() if torch.is_tensor(src) else src)]
+        if host and not (0 <= min(host) and max(host) < add.shape[0]):
+            raise V3DError(f"add_rows: src outside add ({add.shape[0]} rows)")
+        src = torch.tensor(host, dtype=torch.int64).to(x.device, non_blocking=True)
+    if rows.dtype != torch.int64 or src.dtype != torch.int64 or rows.numel() != src.numel():
+        raise V3DError("add_rows: rows and src must be int64 and equally long")
+    check(lib().v3d_add_rows(_p(x), x.stride(0), _p(rows), _p(src), rows.numel(), x.shape[1], _p(add), add.stride(0), _code(x), _stream()),
+          "v3d_add_rows")
+    return x
+
+
 # ------------------------------------------------------------------------------ attention
 
 
@@ -731,6 +756,22 @@ def ground_scores(obj, query):
     n, C = obj.shape
     out = torch.empty(n, dtype=obj.dtype, device=obj.device)
     check(lib().v3d_ground_scores(_p(obj), obj.stride(0), n, _p(query), C, _p(out), _code(obj), _stream()), "v3d_ground_scores")
+    return out
+
+
+def ground_scores_rows(obj, queries, out=None):
+    """scores [G, n] of the object rows obj [n, C] against G query rows [G, C] in one launch; row g = ground_scores(obj, queries[g])
+    bit for bit."""
+    n, C = obj.shape
+    if queries.dim() != 2 or queries.shape[1] != C or queries.dtype != obj.dtype or obj.stride(1) != 1 or queries.stride(1) != 1:
+        raise V3DError(f"ground_scores_rows: obj {tuple(obj.shape)} against queries {tuple(queries.shape)}")
+    G = queries.shape[0]
+    if out is None:
+        out = torch.empty((G, n), dtype=obj.dtype, device=obj.device)
+    elif tuple(out.shape) != (G, n) or out.dtype != obj.dtype or out.stride(1) != 1:
+        raise V3DError(f"ground_scores_rows: out {tuple(out.shape)}")
+    check(lib().v3d_ground_scores_rows(_p(obj), obj.stride(0), n, _p(queries), queries.stride(0), G, C, _p(out), out.stride(0),
+                                       _code(obj), _stream()), "v3d_ground_scores_rows")
     return out
 
 

@@ -39,6 +39,19 @@ class SceneSample:
     extra: dict = field(default_factory=dict)
 
 
+@dataclass
+class SceneJob:
+    """What SceneReusePipeline runs on ONE prefilled scene.  `questions`: the id tensors that follow the shared prefix.
+    Answers (ScanQA, SQA3D; Scan2Cap with `box_inputs` [x, y, z] or None per question + `coord_token_id`) -> token ids per question;
+    grounding (`objects` [n, 6] handed to the scene prefill, `ground_rows[g]` = the <ground> label's row inside question g) -> one
+    score vector per question."""
+    questions: list
+    objects: Optional[torch.Tensor] = None
+    ground_rows: Optional[list] = None
+    box_inputs: Optional[list] = None
+    coord_token_id: Optional[int] = None
+
+
 class _HostBlock:
     """One scene's frames in a shared-memory block that worker processes write and the GPU reads by DMA (registered as pinned)."""
 
@@ -372,27 +385,33 @@ class SceneReusePipeline:
 
     @torch.no_grad()
     def run(self, scenes, max_new_tokens, eos_token_id=None, overlap=True):
-        """scenes: iterable of (SceneSample whose input_ids are the PREFIX ids up to and including <image>, [question id tensors]) - consumed
-        lazily, one scene ahead.  Returns, per scene, the list of its answers' token-id tensors (host, cut after the first EOS)."""
+        """scenes: iterable of (SceneSample whose input_ids are the PREFIX ids up to and including <image>, [question id tensors] or a
+        SceneJob) - consumed lazily, one scene ahead.  Returns, per scene, the list of its answers' token-id tensors (host, cut after the
+        first EOS) or, for a grounding job, of its queries' score vectors (host).  A scene without questions is prefilled and gives []."""
         eng = self.eng
         keep_ctx, keep_ws = eng.ctx, eng.ws
         it = iter(scenes)
         cur = torch.cuda.current_stream()
         sA, sB = (self.sA, self.sB) if overlap else (cur, cur)
         out = []
+        read = [None, None]            # per scene context: the event behind the last batches (stream B) that read it
 
         def queue_prefill(k):
             item = next(it, None)
             if item is None:
                 return None
-            smp, questions = item
+            smp, job = item
+            if not isinstance(job, SceneJob):
+                job = SceneJob(questions=list(job))
             with torch.cuda.stream(sA):
+                if read[k % 2] is not None:
+                    sA.wait_event(read[k % 2])      # scene k - 2's batches read this context (and its object tensors) on stream B
                 eng.use_workspace(self.ws[0])
                 eng.use(self.scene_ctx[k % 2])
                 images, coords = self.inputs.device_inputs(smp)
-                P = eng.prefill_scene(smp.input_ids, images, coords)
+                P = eng.prefill_scene(smp.input_ids, images, coords, objects=job.objects)
                 done = sA.record_event()
-            return k, questions, P, done
+            return k, job, P, done
 
         try:
             if overlap:
@@ -400,20 +419,28 @@ class SceneReusePipeline:
                 sB.wait_stream(cur)
             pending = queue_prefill(0)
             while pending is not None:
-                k, questions, P, done = pending
+                k, job, P, done = pending
                 # the NEXT scene's prefill goes to stream A before this scene's answers are queued: the host then sits in the answer
-                # groups' stop-test polling while stream A works.  Its context was last read by scene k - 1's answers, which the host
-                # has already collected.
+                # groups' stop-test polling while stream A works.  Its context was last read by scene k - 1's batches: stream A waits
+                # for the event recorded behind them (that the host has collected their results as well is not relied upon).
                 pending = queue_prefill(k + 1)
                 answers = []
+                qs_all = job.questions
                 with torch.cuda.stream(sB):
                     sB.wait_event(done)
                     eng.use_workspace(self.ws[1])
                     eng.use(self.scene_ctx[k % 2])
-                    for b0 in range(0, len(questions), self.batch):
-                        qs = questions[b0: b0 + self.batch]
+                    for b0 in range(0, len(qs_all), self.batch):
+                        qs = qs_all[b0: b0 + self.batch]
+                        if job.ground_rows is not None:
+                            answers += list(eng.ground_group(qs, job.ground_rows[b0: b0 + self.batch]).cpu())
+                            continue
                         room = eng.cfg.llm.max_pos - P - max(int(q.numel()) for q in qs) + 1
-                        answers += [a.cpu() for a in eng.answer_group(qs, max_new_tokens=min(max_new_tokens, room), eos_token_id=eos_token_id)]
+                        answers += [a.cpu() for a in eng.answer_group(
+                            qs, max_new_tokens=min(max_new_tokens, room), eos_token_id=eos_token_id,
+                            box_inputs=None if job.box_inputs is None else job.box_inputs[b0: b0 + self.batch],
+                            coord_token_id=job.coord_token_id)]
+                    read[k % 2] = sB.record_event()
                 out.append(answers)
             if overlap:
                 cur.wait_stream(sA)
