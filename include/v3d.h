@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define V3D_ABI_VERSION 7   /* 2: *_rows decode entries, fp8 path, a7 / a3 device entries; 3: rope_kv_store, add_row, ...; 4: resize_bicubic, eos_update, embed_grad bounds; 6: sumsq, *_rows entries take 1..32 rows; 7: attention_shared_prefix; ground_scores_rows and add_rows were ADDED under 7 (no entry changed) */
+#define V3D_ABI_VERSION 7   /* 2: *_rows decode entries, fp8 path, a7 / a3 device entries; 3: rope_kv_store, add_row, ...; 4: resize_bicubic, eos_update, embed_grad bounds; 6: sumsq, *_rows entries take 1..32 rows; 7: attention_shared_prefix; ground_scores_rows, add_rows and the v3d_beam_* entries were ADDED under 7 (no entry changed) */
 
 enum { V3D_F32 = 0, V3D_F16 = 1, V3D_BF16 = 2 };
 enum { V3D_U8_HWC = 16 };   /* v3d_resize_bicubic_u8 only: 8-bit interleaved output, no normalisation */
@@ -381,6 +381,40 @@ int v3d_argmax_rows(const void* x, int64_t ldx, int M, int n, int dtype, int64_t
  * done[m] |= tokens[m] in eos_ids[0:n_eos] (device int64 arrays; done: device int32 [M], kept across steps), *n_done = number
  * of rows that have finished.  The host polls n_done asynchronously instead of synchronising on every token. */
 int v3d_eos_update(const int64_t* tokens, int M, const int64_t* eos_ids, int n_eos, int32_t* done, int32_t* n_done, void* stream);
+
+/* ------------------------------------------------------------------ beam search (a23, num_beams > 1) - */
+/* Added under ABI 7 (no entry changed).  The rule is DESIGN section 2, "Beam search, stated once"; B = num_beams <= 16 (two sets
+ * of 16 K/V slices), K = max(2, 1 + n_eos) * B <= 64 candidates per step.
+ *
+ * v3d_beam_topk: M rows (1: the prefill's row, or B) of 16-bit logits x + b * ldx, V columns; score[b, v] = running[b] +
+ * (x[b, v] - lse_b) in f32 (f32 log-sum-exp per row); the K largest as cand_score[K] / cand_flat[K] (flat = b * V + v), descending,
+ * equal scores in ascending flat order.  Rows with running[b] <= -1e9 are not read.  done (device int32 word, may be NULL): when
+ * set, nothing is written.  workspace: v3d_beam_topk_workspace_bytes(M, V, K), 16-byte aligned.  v3d_beam_topk_chunk: the vocab
+ * columns one workgroup selects from (a row is cut at its multiples). */
+int64_t v3d_beam_topk_workspace_bytes(int M, int V, int K);
+int v3d_beam_topk_chunk(int M, int V);
+int v3d_beam_topk(const void* logits, int64_t ldx, int M, int V, int dtype, const float* running, int K, float* cand_score,
+                  int32_t* cand_flat, const int32_t* done, void* workspace, int64_t workspace_bytes, void* stream);
+/* v3d_beam_step: step `step` (0-based) of the search over the K candidates; one workgroup.  state: v3d_beam_state_bytes(B,
+ * max_new_tokens) bytes of 4-byte words laid out as csrc/beam_step.h says (word 0 = done, an int32 WORD that is 0 or 1, not a count;
+ * word 1 = the heuristic's flag; word 2 = steps executed; then the running scores, which v3d_beam_topk reads as `running`); the
+ * caller initialises it (v3d.ops.beam_state).  div[n] = float32(n ** length_penalty), n <= max_new_tokens (device).  Writes
+ * next_tokens int64[B] and parents int32[B] for the next decode step and row `step` of the trace [max_new_tokens, K].  Once done is
+ * set the call changes nothing.  v3d_beam_step_host: the same body over host memory. */
+int64_t v3d_beam_state_bytes(int B, int max_new_tokens);
+int v3d_beam_step(const float* cand_score, const int32_t* cand_flat, int K, int B, int V, int max_new_tokens, int step,
+                  const int64_t* eos_ids, int n_eos, const float* div, void* state, int64_t* next_tokens, int32_t* parents,
+                  float* trace_score, int32_t* trace_flat, void* stream);
+int v3d_beam_step_host(const float* cand_score, const int32_t* cand_flat, int K, int B, int V, int max_new_tokens, int step,
+                       const int64_t* eos_ids, int n_eos, const float* div, void* state, int64_t* next_tokens, int32_t* parents,
+                       float* trace_score, int32_t* trace_flat);
+/* v3d_beam_kv_gather: for every layer l < n_layers (layer_ptrs: DEVICE array of the layers' base pointers, each [n_slices,
+ * slice_rows, >= width] 16-bit with the given strides in elements), rows [S, S + n) of slice src_base + parents[b] are copied to
+ * slice dst_base + b, b < B, in one launch of 16-byte loads and stores.  The two slice sets must be disjoint.  parents: device
+ * int32[B]; done as above. */
+int v3d_beam_kv_gather(void* const* layer_ptrs, int n_layers, int64_t slice_stride, int64_t row_stride, int width, int n_slices,
+                       int64_t slice_rows, int S, int n, int src_base, int dst_base, int B, const int32_t* parents, const int32_t* done,
+                       void* stream);
 
 /* ------------------------------------------------------------------ grounding (K19, K20) - */
 

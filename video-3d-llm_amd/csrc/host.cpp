@@ -1,5 +1,5 @@
 // Host side of the C ABI: error reporting and the host-only helpers (frame sampling,
-// greedy max-coverage frame selection).
+// greedy max-coverage frame selection, the beam-search step's twin).
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "v3d.h"
+#include "beam_step.h"
 
 namespace v3d {
 
@@ -126,4 +127,22 @@ extern "C" int v3d_greedy_cover_host(const int32_t* keys_host, int n_frames, int
   if (num_all_host) *num_all_host = num_all;
   if (num_sel_host) *num_sel_host = num_sel;
   return picks;
+}
+
+// a23, num_beams > 1: the twin of v3d_beam_step - the same body (beam_step.h) over host memory
+extern "C" int v3d_beam_step_host(const float* cand_score, const int32_t* cand_flat, int K, int B, int V, int max_new_tokens, int step,
+                                  const int64_t* eos_ids, int n_eos, const float* div, void* state, int64_t* next_tokens, int32_t* parents,
+                                  float* trace_score, int32_t* trace_flat) {
+  if (!cand_score || !cand_flat || !div || !state || !next_tokens || !parents || !trace_score || !trace_flat || (!eos_ids && n_eos != 0)) {
+    v3d::set_error("v3d_beam_step_host: null pointer");
+    return V3D_E_INVALID;
+  }
+  if (!v3d::beam_step_args_ok(B, K, V, max_new_tokens, step, n_eos)) {
+    v3d::set_error("v3d_beam_step_host: bad shape (B=%d K=%d V=%d step=%d of %d, %d EOS ids)", B, K, V, step, max_new_tokens, n_eos);
+    return V3D_E_INVALID;
+  }
+  const v3d::BeamView s = v3d::beam_view((int32_t*)state, B, max_new_tokens);
+  if (v3d::beam_step_decide(s, B, K, V, max_new_tokens, step, cand_score, cand_flat, eos_ids, n_eos, div, next_tokens, parents, trace_score, trace_flat))
+    v3d::beam_step_move(s, B, V, max_new_tokens, step, cand_flat, 0, 1);
+  return V3D_OK;
 }

@@ -81,6 +81,46 @@ int main() {
   CHECK(v3d_greedy_cover_host(k3, 0, 1, k3, 1, 1, &one, &g1, &na, &ns) == V3D_E_INVALID);
   CHECK(v3d_greedy_cover_host(k3, 1, 1, k3, 1, 0, &one, &g1, &na, &ns) == V3D_E_INVALID);
   CHECK(v3d_greedy_cover_host(k3, 1, 1, nullptr, 0, 1, &one, &g1, &na, &ns) >= 0);      // an empty scene is legal: nothing to cover
+  // a23, num_beams > 1: scripted steps through the beam step's twin (B = 2, K = 4, V = 10, 4 new tokens, EOS id 3, length_penalty 1)
+  {
+    const int B = 2, K = 4, V = 10, L = 4;
+    const int64_t eos[1] = {3};
+    const float div[L + 1] = {0.f, 1.f, 2.f, 3.f, 4.f};
+    std::vector<int32_t> st(4 + 6 * B + 4 * B * L, 0);
+    st[1] = 1;                                                               // improvable
+    float* run = reinterpret_cast<float*>(st.data() + 4);
+    float* fin = run + B;
+    run[0] = 0.f; run[1] = -1e9f; fin[0] = fin[1] = -1e9f;
+    const int32_t* fin_len = st.data() + 4 + 3 * B;
+    const int32_t* seqs = st.data() + 4 + 6 * B;                             // run_seq[2][B][L], fin_seq[2][B][L]
+    const float sc[4][K] = {{-0.5f, -1.0f, -1.5f, -2.0f}, {-0.7f, -0.9f, -1.6f, -1.8f}, {-2.5f, -2.6f, -2.7f, -2.8f}, {-2.6f, -2.7f, -2.9f, -3.0f}};
+    const int32_t fl[4][K] = {{4, 3, 7, 1}, {13, 5, 3, 12}, {5, 6, 15, 16}, {1, 12, 2, 13}};
+    int64_t next[B] = {-1, -1};
+    int32_t par[B] = {-1, -1};
+    std::vector<float> ts(L * K, 0.f);
+    std::vector<int32_t> tf(L * K, 0);
+    auto step = [&](int t) { return v3d_beam_step_host(sc[t], fl[t], K, B, V, L, t, eos, 1, div, st.data(), next, par, ts.data(), tf.data()); };
+    CHECK(step(0) == V3D_OK);                                                // rank-1 EOS finishes with -1.0; tokens 4 and 7 run on
+    CHECK(st[0] == 0 && st[2] == 1 && next[0] == 4 && next[1] == 7 && par[0] == 0 && par[1] == 0);
+    CHECK(run[0] == -0.5f && run[1] == -1.5f && fin[0] == -1.0f && fin[1] == -1e9f && fin_len[0] == 1);
+    CHECK(step(1) == V3D_OK);                                                // EOS at rank 0 finishes (-0.7 / 2); the EOS at rank 2 >= B must not
+    CHECK(st[0] == 0 && next[0] == 5 && next[1] == 2 && par[0] == 0 && par[1] == 1);
+    CHECK(fin[0] == -0.35f && fin[1] == -1.0f && fin_len[0] == 2 && fin_len[1] == 1);
+    const int32_t* run2 = seqs + 0 * B * L;                                  // two steps done: buffers 0
+    const int32_t* fin2 = seqs + 2 * B * L;
+    CHECK(run2[0] == 4 && run2[1] == 5 && run2[L] == 7 && run2[L + 1] == 2 && fin2[0] == 7 && fin2[1] == 3 && fin2[L] == 3);
+    CHECK(step(2) == V3D_OK && st[0] == 0 && next[0] == 5 && next[1] == 6 && par[0] == 0 && par[1] == 0 && fin[0] == -0.35f);
+    CHECK(step(3) == V3D_OK);                                                // the length limit: every candidate stops, the search ends
+    CHECK(st[0] == 1 && st[2] == 4 && fin[0] == -0.35f && fin[1] == -2.6f / 4.f && fin_len[0] == 2 && fin_len[1] == 4);
+    const std::vector<int32_t> frozen = st;
+    next[0] = 77;
+    CHECK(step(3) == V3D_OK && st == frozen && next[0] == 77);               // done: nothing moves any more
+    CHECK(tf[3 * K + 1] == 12 && ts[1 * K + 0] == -0.7f);
+    CHECK(v3d_beam_step_host(sc[0], fl[0], K, 17, V, L, 0, eos, 1, div, st.data(), next, par, ts.data(), tf.data()) == V3D_E_INVALID);
+    CHECK(v3d_beam_step_host(sc[0], fl[0], 1, B, V, L, 0, eos, 1, div, st.data(), next, par, ts.data(), tf.data()) == V3D_E_INVALID);
+    CHECK(v3d_beam_step_host(sc[0], fl[0], K, B, V, L, L, eos, 1, div, st.data(), next, par, ts.data(), tf.data()) == V3D_E_INVALID);
+    CHECK(v3d_beam_step_host(nullptr, fl[0], K, B, V, L, 0, eos, 1, div, st.data(), next, par, ts.data(), tf.data()) == V3D_E_INVALID);
+  }
   std::puts("host_selftest ok");
   return 0;
 }

@@ -14,8 +14,9 @@ v3d.engine.Engine's HBM layouts.  Call contracts mirrored (3-D eval drivers):
     model(input_ids, images=..., modalities="video", video_dict=..., labels=labels, use_object_proposals=True)
                                                                                          -> (None, scores [n_obj + 1])
     model(input_ids, images=..., modalities="video", video_dict=..., [labels=...])       -> CausalLMOutputWithPast(loss, logits [1,S,V] f32)
-Greedy decoding only, no autograd (the loss is a forward value); sampling / beams / box_labels raise NotImplementedError, unknown keyword arguments raise
-TypeError - nothing is silently dropped.
+generate is greedy only, no autograd (the loss is a forward value); sampling / beams / box_labels raise NotImplementedError there, unknown keyword
+arguments raise TypeError - nothing is silently dropped.  Beam search has its own entry, model.generate_beam(..., num_beams=N, length_penalty=p):
+generate's arguments and return.
 """
 import json
 import os
@@ -222,7 +223,25 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
         if unknown:
             raise TypeError(f"LlavaQwenForCausalLM.generate: unsupported arguments {sorted(unknown)} (accepted: {sorted(self._GENERATE_KW)})")
         if kwargs.get("do_sample") or (kwargs.get("num_beams") or 1) != 1:
-            raise NotImplementedError("greedy decoding only (the 3-D eval drivers run temperature 0, num_beams 1)")
+            raise NotImplementedError("greedy decoding only (the 3-D eval drivers run temperature 0, num_beams 1); beam search is "
+                                      "generate_beam(input_ids, images=..., video_dict=..., num_beams=N)")
+        return self._generate(inputs, images, kwargs)
+
+    @torch.no_grad()
+    def generate_beam(self, inputs=None, images=None, image_sizes=None, modalities=("image",), num_beams=1, length_penalty=1.0, **kwargs):
+        """generate(...) with num_beams beams (Engine.beam_search: transformers' beam search for do_sample=False, early_stopping=False,
+        num_return_sequences=1): the same arguments, the same [1, n_new] return.  num_beams=1 is generate()."""
+        unknown = set(kwargs) - self._GENERATE_KW
+        if unknown:
+            raise TypeError(f"LlavaQwenForCausalLM.generate_beam: unsupported arguments {sorted(unknown)} (accepted: {sorted(self._GENERATE_KW)})")
+        if kwargs.get("do_sample"):
+            raise NotImplementedError("beam search here is deterministic (do_sample=False)")
+        if int(num_beams) > 1 and kwargs.get("stopping_criteria"):
+            raise NotImplementedError("stopping_criteria cannot be combined with beams: they stop by EOS ids and max_new_tokens only")
+        return self._generate(inputs, images, kwargs, num_beams=int(num_beams), length_penalty=float(length_penalty))
+
+    def _generate(self, inputs, images, kwargs, num_beams=1, length_penalty=1.0):
+        """The argument handling generate and generate_beam share, then Engine.generate."""
         if kwargs.get("use_cache") is False:
             raise NotImplementedError("use_cache=False: the engine always decodes through its KV cache")
         am = kwargs.get("attention_mask")
@@ -248,9 +267,10 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
             stopping = lambda toks: any(bool(torch.as_tensor(c(toks[None], None)).any()) for c in crit)      # noqa: E731
         box_input = video_dict.get("box_input") if hasattr(video_dict, "get") else None
         coord_ids = getattr(self.config, "coord_token_ids", None)
+        beams = dict(num_beams=num_beams, length_penalty=length_penalty) if num_beams > 1 else {}
         out = self.engine.generate(ids, frames, coords, max_new_tokens=max_new, eos_token_id=self._eos(kwargs.get("eos_token_id")),
                                    stopping=stopping, box_input=box_input if box_input is not None and len(box_input) else None,
-                                   coord_token_id=coord_ids[0] if coord_ids else None)
+                                   coord_token_id=coord_ids[0] if coord_ids else None, **beams)
         return out.view(1, -1)
 
     def prepare_inputs_for_generation(self, *a, **kw):

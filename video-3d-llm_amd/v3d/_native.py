@@ -130,6 +130,13 @@ SIGNATURES = {
     "v3d_greedy_cover_workspace_bytes": (c_l, [c_i, c_l]),
     "v3d_greedy_cover": (c_i, [c_p, c_i, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_l, c_p]),
     "v3d_greedy_cover_host": (c_i, [c_p, c_i, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_p]),
+    "v3d_beam_topk_workspace_bytes": (c_l, [c_i, c_i, c_i]),
+    "v3d_beam_topk_chunk": (c_i, [c_i, c_i]),
+    "v3d_beam_topk": (c_i, [c_p, c_l, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_l, c_p]),
+    "v3d_beam_state_bytes": (c_l, [c_i, c_i]),
+    "v3d_beam_step": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "v3d_beam_step_host": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "v3d_beam_kv_gather": (c_i, [c_p, c_i, c_l, c_l, c_i, c_i, c_l, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
 }
 
 

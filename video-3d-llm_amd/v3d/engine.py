@@ -720,18 +720,32 @@ class Engine:
     # ------------------------------------------------------------------ generate (a23)
     @torch.no_grad()
     def generate(self, input_ids, images, world_coords, max_new_tokens=16, eos_token_id=None, stopping=None, box_input=None,
-                 coord_token_id=None):
+                 coord_token_id=None, num_beams=1, length_penalty=1.0, return_trace=False):
         """Greedy decoding of one (scene, question): LlavaQwenForCausalLM.generate (llava_qwen.py:208-236)
         with do_sample=False, num_beams=1 as model_scanqa.py:173-185 calls it.  eos_token_id: an int or a collection of ints;
         stopping: optional host callback(token_ids_so_far: LongTensor [n]) -> bool, checked after every token (HF's
-        stopping_criteria; forces one host synchronisation per step)."""
+        stopping_criteria; forces one host synchronisation per step).
+        num_beams > 1 (the drivers' --num_beams): the same prefill, then beam_search (length_penalty, return_trace: see there);
+        stopping callbacks cannot be combined with beams."""
+        self._check_beams(num_beams, stopping, return_trace)
         feats = self.encode_images(images)
         ids = self.voxel_ids(world_coords.to(self.dtype))
         x = self.build_inputs_embeds(input_ids, feats, ids, box_input=box_input, coord_token_id=coord_token_id)
         S = x.shape[0]
         self._check_room(S, max_new_tokens)
         logits = self.llm_forward(x, 0, last_rows=[S - 1])
+        if num_beams > 1:
+            return self.beam_search(logits, S, num_beams, max_new_tokens, eos_token_id, length_penalty, return_trace)
         return self.decode_loop(logits, S, max_new_tokens, eos_token_id, stopping)
+
+    @staticmethod
+    def _check_beams(num_beams, stopping, return_trace=False):
+        if not isinstance(num_beams, int) or num_beams < 1:
+            raise V3DError(f"num_beams must be a positive integer (got {num_beams!r})")
+        if num_beams > 1 and stopping is not None:
+            raise V3DError("a stopping callback cannot be combined with num_beams > 1: beams stop by EOS ids and max_new_tokens only")
+        if num_beams == 1 and return_trace:
+            raise V3DError("return_trace belongs to beam search (num_beams > 1)")
 
     # ------------------------------------------------------------------ scene-level reuse (SURVEY 8 f1)
     @torch.no_grad()
@@ -764,11 +778,16 @@ class Engine:
         return self.ctx.prefix_len
 
     @torch.no_grad()
-    def answer(self, question_ids, max_new_tokens=16, eos_token_id=None, stopping=None):
+    def answer(self, question_ids, max_new_tokens=16, eos_token_id=None, stopping=None, num_beams=1, length_penalty=1.0, return_trace=False,
+               box_input=None, coord_token_id=None):
         """Greedy answer to one question about the scene prefilled by prefill_scene: only the question's rows (the ids that follow
         the prefix in the full prompt) run through the decoder, at positions P.., attending to the cached prefix; then the
         usual decode loop.  Causality makes the prefix rows of the uncached pass independent of the question, so the tokens are
-        those of generate(prefix_ids + question_ids, ...) (tests/test_gpu_scene_reuse.py).  The prefix rows are left intact."""
+        those of generate(prefix_ids + question_ids, ...) (tests/test_gpu_scene_reuse.py).  The prefix rows are left intact.
+        num_beams > 1: beam_search behind the same question rows, as generate does.
+        box_input [x, y, z] + coord_token_id (Scan2Cap): the PE of the discretised box centre on the question's <coord> rows, as
+        build_inputs_embeds adds it for a whole prompt."""
+        self._check_beams(num_beams, stopping, return_trace)
         P = getattr(self.ctx, "prefix_len", 0)
         if not P or self.ctx.kv_len < P:
             raise V3DError("answer() needs prefill_scene() on this context first")
@@ -778,7 +797,17 @@ class Engine:
             raise V3DError("answer() needs at least one question token")
         self._check_room(P + Q, max_new_tokens)
         x = ops.embed_gather(self.embed, q, out=self.l_x[P: P + Q])
+        if coord_token_id is not None and box_input is not None and len(box_input):
+            rows = [r for r, t in enumerate(question_ids.tolist()) if t == coord_token_id]
+            if rows:
+                c = self.cfg
+                centre = ops.discrete_coords(torch.as_tensor(box_input, dtype=torch.float32).to(device=self.device, dtype=self.dtype).reshape(-1, 3)[:1].contiguous(),
+                                             c.min_xyz, c.max_xyz, c.voxel_size)
+                pe = ops.sin3d_pe(centre[None], c.llm.hidden, dim_t=self.pe_table.dim_t)[0, 0]
+                ops.add_row(x, torch.tensor(rows, dtype=torch.int64, device=self.device), pe)
         logits = self.llm_forward(x, P, last_rows=[Q - 1])
+        if num_beams > 1:
+            return self.beam_search(logits, P + Q, num_beams, max_new_tokens, eos_token_id, length_penalty, return_trace)
         return self.decode_loop(logits, P + Q, max_new_tokens, eos_token_id, stopping)
 
     MAX_GROUP = 32          # scenes / questions whose decode steps share a pass over the weights (r04: 32; csrc DEC_MAX_ROWS)
@@ -1138,3 +1167,82 @@ class Engine:
         if st is not None:
             out = self.trim_at_eos(out[None], eos)[0].to(self.device)
         return out
+
+    # ------------------------------------------------------------------ beam search (a23, num_beams > 1)
+    @torch.no_grad()
+    def beam_search(self, logits, S, num_beams, max_new_tokens, eos_token_id=None, length_penalty=1.0, return_trace=False, lookahead=2):
+        """Beam search behind a prompt of S rows whose K/V is in the current context and whose last-row logits are `logits` (a view of
+        ctx.logits[0]): the rule of DESIGN section 2 "Beam search, stated once" (transformers' _beam_search for batch 1, do_sample=False,
+        early_stopping=False, no logits processors; equal scores go to the lower flat index).  Returns the new tokens of the best
+        finished hypothesis, cut after its first EOS as generate returns them; with return_trace a dict as well: its score and length,
+        the candidates of every executed step (cand_score / cand_flat [steps, K]) and the final state (ops.beam_state_views).
+        The B beams are rows of the answer_group decode group that share the prompt: its keys are read from the context's ONE cache
+        (shared_prefix = S), the beams' own rows [S, S + n) live in the 32 K/V slices used as two sets of 16 - the decode after step t
+        writes and reads set t & 1, and v3d_beam_kv_gather moves the chosen parents' rows from set (t - 1) & 1 into it first.  So every
+        pointer and position passed by value depends on the step number only; parents, tokens and scores never leave the device, and
+        the done word is read `lookahead` - 1 steps late through a pinned copy (the kernels do nothing once it is set).  Nothing is
+        allocated inside the loop."""
+        l = self.cfg.llm
+        B = int(num_beams)
+        eos = () if eos_token_id is None else ((int(eos_token_id),) if isinstance(eos_token_id, int) else tuple(int(e) for e in eos_token_id))
+        K = max(2, 1 + len(eos)) * B
+        if not 1 <= B <= ops.BEAM_MAX_B or K > ops.BEAM_MAX_K:
+            raise V3DError(f"beam search takes 1 to {ops.BEAM_MAX_B} beams and at most {ops.BEAM_MAX_K} candidates per step "
+                           f"(num_beams={B}, {len(eos)} EOS ids: K = max(2, 1 + n_eos) * num_beams = {K})")
+        self._check_room(S, max_new_tokens)
+        scene = self.ctx
+        if scene.kv_len < S:
+            raise V3DError("beam_search() needs the prompt's K/V rows in the current context")
+        st = self._answer_state(B)
+        if scene.kv[0].stride(0) != st.kv[0].stride(1):
+            raise V3DError("beam_search: the context's cache and the decode group's slices must share a row stride")
+        key = (B, max_new_tokens, K, l.vocab, eos, float(length_penalty))
+        bs = getattr(st, "beam", None)
+        if bs is None or st.beam_key != key:
+            bs = st.beam = ops.BeamState(B, max_new_tokens, K, l.vocab, eos, length_penalty, device=self.device)
+            st.beam_key = key
+            st.beam_host = torch.zeros((max_new_tokens, 1), dtype=torch.int32).pin_memory()
+            st.beam_events = [torch.cuda.Event() for _ in range(max_new_tokens)]
+        else:
+            bs.reset()
+        if getattr(st, "kv_ptrs", None) is None:
+            st.kv_ptrs = ops.beam_kv_layers(st.kv)
+        half = st.n // 2
+        rows = st.rows
+        # the rows of the 64-row tile that straddles S, for every beam of both sets (what _question_rows hands to a question's cache)
+        S0 = (S // 64) * 64
+        if S > S0:
+            for i in range(l.layers):
+                for base in (0, half):
+                    ops.copy_rows_bcast(scene.kv[i][S0:S], st.kv[i][base: base + B, S0:])
+        x = logits if logits.dim() == 2 else logits[None]
+        n_steps = max_new_tokens
+        for t in range(max_new_tokens):
+            ops.beam_topk(x, bs.running, K, bs.cand_score, bs.cand_flat, bs.topk_ws, done=bs.done, V=l.vocab)
+            ops.beam_step(bs, t)
+            st.beam_host[t].copy_(bs.done, non_blocking=True)
+            st.beam_events[t].record()
+            back = t - (lookahead - 1)
+            if back >= 0:
+                st.beam_events[back].synchronize()
+                if int(st.beam_host[back]):                     # the search ended at step `back`: what was queued since changed nothing
+                    n_steps = t + 1
+                    break
+            if t + 1 == max_new_tokens:
+                break
+            cur = (t & 1) * half
+            if t >= 1:
+                ops.beam_kv_gather(st.kv, st.kv_ptrs, S, t, half - cur, cur, bs.parents, done=bs.done)
+            ops.embed_gather(self.embed, bs.next_tokens, out=rows.x[:B])
+            x = self.decode_forward_rows(rows, st.ctxs[cur: cur + B], [S + t] * B, shared_prefix=S, prefix_kv=scene.kv)
+        self.use(scene)
+        words = bs.state.cpu()                                  # one read: scores, lengths and sequences of the finished hypotheses
+        v = ops.beam_state_views(words, B, max_new_tokens)
+        n = int(v["fin_len"][0])
+        toks = self.trim_at_eos(v["fin_seq"][0, :n].to(torch.int64)[None], eos)[0].to(self.device)
+        if not return_trace:
+            return toks
+        T = v["steps"]
+        return toks, dict(score=float(v["fin_score"][0]), length=n, steps=T, queued_steps=n_steps, K=K, cand_score=bs.trace_score[:T].cpu(),
+                          cand_flat=bs.trace_flat[:T].cpu(), state=v)
+

@@ -23,6 +23,9 @@ in batches of up to 32 over its cached prefix, pipelined (v3d.pipeline.SceneReus
                             Engine.ground_group scores a batch of queries against them
 The records keep their keys and order; sharding defaults to whole scenes per rank.
 
+--num_beams N (generation tasks; the reference drivers' flag): beam search per question - model.generate_beam in the plain loop, or with
+--reuse-scenes one scene prefill and Engine.answer(num_beams=N) per question.  The cross-scene decode group is not used with beams.
+
 `v3d.eval_ground`, `v3d.eval_scan2cap`, `v3d.eval_sqa3d` are entry points with the task fixed.
 """
 import argparse
@@ -214,7 +217,7 @@ def answer_fn_for(task, model, tokenizer, image_processor, video_processor, mode
                                 reuse_scenes=a.reuse_scenes, pipeline=not a.no_pipeline)
     kw = dict(max_frame_num=a.max_frame_num, max_new_tokens=a.max_new_tokens, reuse_scenes=a.reuse_scenes, times=times,
               pipeline=not a.no_pipeline, group_size=a.decode_group, workers=(0 if a.loader_workers < 0 else a.loader_workers or None),
-              pool=pool, stats=stats)
+              pool=pool, stats=stats, num_beams=a.num_beams, length_penalty=a.length_penalty)
     if task == "scan2cap":                      # model_scan2cap.py:137-139, 199-212
         def record(line, text):
             r = E.make_record(line, text, model_name)
@@ -248,9 +251,12 @@ def main(argv=None, task=None):
     ap.add_argument("--shard", choices=("stride", "scene"), default=None)
     ap.add_argument("--llm-weights", choices=E.LLM_WEIGHTS, default="bf16", help="decoder linears: 16-bit (default), e4m3 (fp8) or MXFP4 (fp4); not reference paths")
     ap.add_argument("--n_gpu", type=int, default=None, help="the reference's flag: started plainly with N > 1, launch N ranks of this runner")
+    E.add_beam_arguments(ap)
     a = ap.parse_args(argv)
     fixed_task = task
     task = task or a.task
+    if a.num_beams > 1 and task in GROUND_TASKS:
+        ap.error("--num_beams belongs to the generation tasks (scanqa, sqa3d, scan2cap)")
     if os.path.exists(a.answer_file):
         print(f"The {a.answer_file} already exists!!!")
         return 0
@@ -264,7 +270,7 @@ def main(argv=None, task=None):
     with open(os.path.expanduser(a.question_file)) as f:
         questions = json.load(f)[: a.test_size]
     pool = None
-    if a.loader_workers >= 0 and not (task in GEN_TASKS and a.no_pipeline):
+    if a.loader_workers >= 0 and not (task in GEN_TASKS and (a.no_pipeline or a.num_beams > 1)):
         from . import frame_io
         pool = frame_io.make_pool(a.loader_workers or E.default_workers())          # forked before this process touches the GPU
     rank, world, dev, gather_dev = E.rank_setup(a.n_gpu)

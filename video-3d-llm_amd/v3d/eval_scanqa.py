@@ -165,7 +165,7 @@ def default_workers():
 
 def model_answer_fn(model, tokenizer, image_processor, video_processor, model_name, max_frame_num=32, max_new_tokens=512,
                     reuse_scenes=False, times=None, pipeline=True, group_size=16, workers=None, stats=None, record_fn=None, pool=None,
-                    box_input_fn=None, skip_fn=None):
+                    box_input_fn=None, skip_fn=None, num_beams=1, length_penalty=1.0):
     """The per-rank loop of model_scanqa.py:130-206 around `model` (the loader-produced LlavaQwenForCausalLM).
     reuse_scenes: one scene prefill per run of consecutive questions about a scene (pipelined or, with pipeline=False, synchronous).
     pipeline (default): v3d.pipeline - asynchronous host loader, prefill / grouped-decode overlap, device-side stop test; the
@@ -174,7 +174,10 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
     pool: v3d.frame_io.make_pool(...) of decoding processes (make it BEFORE the process initialises the GPU); default: one per call;
     workers = 0 decodes on the calling thread.
     box_input_fn(line) -> [x, y, z] or None: the Scan2Cap prompt's box centre (model_scan2cap.py:137-139, 170; its PE is added to the
-    <coord> token rows); skip_fn(line) -> True: the question is not run and its answer is "" (:199-200)."""
+    <coord> token rows); skip_fn(line) -> True: the question is not run and its answer is "" (:199-200).
+    num_beams > 1 (the drivers' --num_beams; length_penalty with it): beam search per question - the plain one-question loop calling
+    model.generate_beam, or with reuse_scenes one scene prefill and Engine.answer(num_beams=N) per question.  The pipeline's cross-scene
+    decode group and answer_group's batches are greedy and are not used with beams."""
     record_fn = record_fn or (lambda line, text: make_record(line, text, model_name))
     coord_ids = getattr(getattr(model, "config", None), "coord_token_ids", None)
 
@@ -198,8 +201,13 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
                                            box_input=box_input_fn(line) if box_input_fn else None)
                 t0 = time.time()
                 with torch.inference_mode():
-                    toks = model.generate(ids, images=images, modalities="video", do_sample=False, temperature=0.0, top_p=None, num_beams=1,
-                                          max_new_tokens=max_new_tokens, use_cache=True, video_dict=vd)
+                    if num_beams > 1:
+                        toks = model.generate_beam(ids, images=images, modalities="video", do_sample=False, temperature=0.0, top_p=None,
+                                                   num_beams=num_beams, length_penalty=length_penalty, max_new_tokens=max_new_tokens,
+                                                   use_cache=True, video_dict=vd)
+                    else:
+                        toks = model.generate(ids, images=images, modalities="video", do_sample=False, temperature=0.0, top_p=None, num_beams=1,
+                                              max_new_tokens=max_new_tokens, use_cache=True, video_dict=vd)
                 if times is not None:
                     torch.cuda.synchronize()
                     times.append(time.time() - t0)
@@ -237,6 +245,11 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
                     qs = [x[at + 1:] for x in ids[b - i: min(j, b + nb) - i]]
                     room = eng.cfg.llm.max_pos - P - max(len(q) for q in qs) + 1
                     boxes, coord_id = _boxes(lines[b: b + len(qs)])
+                    if num_beams > 1:                    # beams: one question at a time behind the scene's prefix
+                        out += [decode(eng.answer(q, max_new_tokens=min(max_new_tokens, eng.cfg.llm.max_pos - P - len(q) + 1), eos_token_id=eos,
+                                                  num_beams=num_beams, length_penalty=length_penalty,
+                                                  box_input=None if boxes is None else boxes[k], coord_token_id=coord_id)) for k, q in enumerate(qs)]
+                        continue
                     answers = eng.answer_group(qs, max_new_tokens=min(max_new_tokens, room), eos_token_id=eos, box_inputs=boxes,
                                                coord_token_id=coord_id)
                     out += [decode(a) for a in answers]
@@ -343,12 +356,22 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
                           "wall_seconds": time.time() - t0})
         return [decode(t) for scene_answers in answers for t in scene_answers]
 
+    if num_beams > 1:
+        return scene_batches if reuse_scenes else one_by_one
     if reuse_scenes:
         return scene_pipelined if pipeline else scene_batches
     return pipelined if pipeline else one_by_one
 
 
 LLM_WEIGHTS = ("bf16", "fp8", "fp4")
+
+
+def add_beam_arguments(ap):
+    ap.add_argument("--num_beams", type=int, default=1,
+                    help="the reference drivers' flag (model_scanqa.py:173-185): beams per question for the generation tasks; N > 1 runs one question "
+                         "at a time (with --reuse-scenes: one scene prefill, then one beam search per question) - the cross-scene decode group "
+                         "is greedy and is not used with beams")
+    ap.add_argument("--length_penalty", type=float, default=1.0, help="beam search: a finished hypothesis scores sum(log p) / n ** length_penalty")
 
 
 def load_model(model_path, overwrite_cfg=False, llm_weights="bf16"):
@@ -397,6 +420,7 @@ def main(argv=None):
                     help="decoder linears: 16-bit as the checkpoint stores them (default), OCP e4m3 (fp8) or OCP MXFP4 (fp4); the last two are not reference paths")
     ap.add_argument("--n_gpu", type=int, default=None,
                     help="the reference's flag (model_scanqa.py:222): started plainly with N > 1, launch N ranks of this runner on this node")
+    add_beam_arguments(ap)
     a = ap.parse_args(argv)
     if os.path.exists(a.answer_file):                                                         # model_scanqa.py:238-240
         print(f"The {a.answer_file} already exists!!!")
@@ -407,7 +431,7 @@ def main(argv=None):
     with open(os.path.expanduser(a.question_file)) as f:
         questions = json.load(f)[: a.test_size]
     pool = None
-    if not a.no_pipeline and a.loader_workers >= 0:
+    if not a.no_pipeline and a.loader_workers >= 0 and a.num_beams == 1:
         from . import frame_io
         pool = frame_io.make_pool(a.loader_workers or default_workers())        # forked before this process touches the GPU
     rank, world, dev, gather_dev = rank_setup(a.n_gpu)
@@ -417,7 +441,8 @@ def main(argv=None):
                         metadata_dir=a.metadata_folder)
     times = []
     fn = model_answer_fn(model, tokenizer, image_processor, vp, name, a.max_frame_num, a.max_new_tokens, a.reuse_scenes, times,
-                         pipeline=not a.no_pipeline, group_size=a.decode_group, workers=(0 if a.loader_workers < 0 else a.loader_workers or None), pool=pool)
+                         pipeline=not a.no_pipeline, group_size=a.decode_group, workers=(0 if a.loader_workers < 0 else a.loader_workers or None), pool=pool,
+                         num_beams=a.num_beams, length_penalty=a.length_penalty)
     records = evaluate(questions, fn, rank, world, gather_dev, shard=a.shard or ("scene" if a.reuse_scenes else "stride"))
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(a.answer_file)), exist_ok=True)

@@ -727,6 +727,131 @@ def argmax(x, out, workspace=None):
     return out
 
 
+# ------------------------------------------------------------------------------ beam search (csrc/beam.hip, csrc/beam_step.h)
+
+BEAM_MAX_B, BEAM_MAX_K, BEAM_NEG = 16, 64, -1.0e9
+_BEAM_HDR = 4           # state words: done, improvable, steps executed, (spare)
+
+
+def beam_topk_chunk(M, V):
+    """The vocab columns one workgroup of v3d_beam_topk selects from: a row of V logits is cut at the multiples of this."""
+    return int(lib().v3d_beam_topk_chunk(int(M), int(V)))
+
+
+class BeamState:
+    """The device state of one beam search (v3d_beam_step) and the buffers of its steps, allocated once: B beams, up to L new tokens,
+    K candidates per step.  views() reads everything back as host tensors."""
+
+    def __init__(self, B, L, K, V, eos_ids=(), length_penalty=1.0, device="cuda"):
+        if not 1 <= B <= BEAM_MAX_B or not B <= K <= BEAM_MAX_K:
+            raise V3DError(f"beam search takes 1 to {BEAM_MAX_B} beams and at most {BEAM_MAX_K} candidates per step (num_beams={B}, K={K}: "
+                           "K = max(2, 1 + number of EOS ids) * num_beams)")
+        if L < 1 or V < K:
+            raise V3DError(f"beam search: max_new_tokens={L}, vocab={V}, K={K}")
+        self.B, self.L, self.K, self.V = B, L, K, V
+        n = int(lib().v3d_beam_state_bytes(B, L))
+        if n <= 0:
+            raise V3DError("v3d_beam_state_bytes: bad shape")
+        self.init = torch.zeros(n // 4, dtype=torch.int32).pin_memory() if torch.cuda.is_available() else torch.zeros(n // 4, dtype=torch.int32)
+        self.init[1] = 1
+        f = self.init.view(torch.float32)
+        f[_BEAM_HDR: _BEAM_HDR + 2 * B] = BEAM_NEG
+        f[_BEAM_HDR] = 0.0
+        self.state = torch.empty(n // 4, dtype=torch.int32, device=device)
+        self.running = self.state[_BEAM_HDR: _BEAM_HDR + B].view(torch.float32)
+        self.done = self.state[:1]
+        self.eos = torch.tensor([int(e) for e in eos_ids], dtype=torch.int64, device=device)
+        # div[n] = float32(n ** length_penalty): the device only divides
+        self.div = torch.tensor([0.0] + [float(n) ** float(length_penalty) for n in range(1, L + 1)], dtype=torch.float64).to(torch.float32).to(device)
+        self.cand_score = torch.empty(K, dtype=torch.float32, device=device)
+        self.cand_flat = torch.empty(K, dtype=torch.int32, device=device)
+        self.next_tokens = torch.zeros(B, dtype=torch.int64, device=device)
+        self.parents = torch.zeros(B, dtype=torch.int32, device=device)
+        self.trace_score = torch.zeros((L, K), dtype=torch.float32, device=device)
+        self.trace_flat = torch.zeros((L, K), dtype=torch.int32, device=device)
+        self.topk_ws = torch.empty(max(int(lib().v3d_beam_topk_workspace_bytes(B, V, K)), 16) // 4, dtype=torch.int32, device=device)
+        self.reset()
+
+    def reset(self):
+        self.state.copy_(self.init, non_blocking=True)
+        return self
+
+    def views(self, state=None):
+        """The state words as a dict of host tensors (one device read unless `state`, a host copy, is given)."""
+        return beam_state_views(self.state.cpu() if state is None else state, self.B, self.L)
+
+
+def beam_state_views(words, B, L):
+    """csrc/beam_step.h's layout over a host int32 tensor: done / improvable / steps, the scores, flags and lengths, and the LIVE
+    sequence buffers (index steps & 1)."""
+    w = words
+    o = _BEAM_HDR
+    f = w.view(torch.float32)
+    T = int(w[2])
+    seq = w[o + 6 * B:].view(4, B, L)
+    return dict(done=int(w[0]), improvable=int(w[1]), steps=T, run_score=f[o: o + B], fin_score=f[o + B: o + 2 * B], fin_flag=w[o + 2 * B: o + 3 * B],
+                fin_len=w[o + 3 * B: o + 4 * B], run_seq=seq[T & 1], fin_seq=seq[2 + (T & 1)])
+
+
+def beam_topk(logits, running, K, cand_score, cand_flat, workspace, done=None, V=None):
+    """logits [M, >=V] 16-bit rows (M = 1 or the number of beams), running f32 [>=M]: the K largest running[b] + log_softmax(row b)[v]
+    as (cand_score f32[K], cand_flat int32[K] = b * V + v), descending, equal scores in ascending flat order (v3d_beam_topk)."""
+    x = logits if logits.dim() == 2 else logits[None]
+    V = x.shape[1] if V is None else int(V)
+    if x.stride(1) != 1 or x.shape[1] < V or running.dtype != torch.float32 or running.numel() < x.shape[0]:
+        raise V3DError(f"beam_topk: logits {tuple(x.shape)}, running {tuple(running.shape)}")
+    if cand_score.numel() < K or cand_flat.numel() < K or cand_score.dtype != torch.float32 or cand_flat.dtype != torch.int32:
+        raise V3DError("beam_topk: cand_score f32 [K] and cand_flat int32 [K]")
+    need = int(lib().v3d_beam_topk_workspace_bytes(x.shape[0], V, K))
+    if need <= 0 or workspace.numel() * workspace.element_size() < need:
+        raise V3DError(f"beam_topk: M={x.shape[0]} V={V} K={K} needs a workspace of {need} bytes")
+    check(lib().v3d_beam_topk(_p(x), x.stride(0), x.shape[0], V, _code(x), _p(running), int(K), _p(cand_score), _p(cand_flat), _p(done), _p(workspace),
+                              workspace.numel() * workspace.element_size(), _stream()), "v3d_beam_topk")
+    return cand_score, cand_flat
+
+
+def beam_step(bs, step):
+    """Step `step` of the search of BeamState bs over bs.cand_score / bs.cand_flat (v3d_beam_step): advances bs.state, writes
+    bs.next_tokens / bs.parents and trace row `step`; a no-op once bs.done is set."""
+    check(lib().v3d_beam_step(_p(bs.cand_score), _p(bs.cand_flat), bs.K, bs.B, bs.V, bs.L, int(step), _p(bs.eos) if bs.eos.numel() else None,
+                              bs.eos.numel(), _p(bs.div), _p(bs.state), _p(bs.next_tokens), _p(bs.parents), _p(bs.trace_score), _p(bs.trace_flat),
+                              _stream()), "v3d_beam_step")
+    return bs
+
+
+def beam_step_host(words, cand_score, cand_flat, B, V, L, step, eos_ids, div, trace_score, trace_flat):
+    """The host twin (v3d_beam_step_host) over host tensors: words int32 (the state, advanced in place), cand_* [K], div f32 [L + 1],
+    trace_* [L, K] -> (next_tokens int64 [B], parents int32 [B])."""
+    K = cand_score.numel()
+    nxt, par = torch.zeros(B, dtype=torch.int64), torch.zeros(B, dtype=torch.int32)
+    eos = torch.tensor([int(e) for e in eos_ids], dtype=torch.int64)
+    for t_, dt in ((words, torch.int32), (cand_score, torch.float32), (cand_flat, torch.int32), (div, torch.float32), (trace_score, torch.float32),
+                   (trace_flat, torch.int32)):
+        if t_.is_cuda or t_.dtype != dt or not t_.is_contiguous():
+            raise V3DError("beam_step_host: contiguous host tensors of the documented types")
+    if words.numel() * 4 < int(lib().v3d_beam_state_bytes(B, L)) or div.numel() < L + 1 or trace_score.numel() < L * K or trace_flat.numel() < L * K:
+        raise V3DError("beam_step_host: a buffer is too small")
+    check(lib().v3d_beam_step_host(_p(cand_score), _p(cand_flat), K, B, V, L, int(step), _p(eos) if eos.numel() else None, eos.numel(), _p(div), _p(words),
+                                   _p(nxt), _p(par), _p(trace_score), _p(trace_flat)), "v3d_beam_step_host")
+    return nxt, par
+
+
+def beam_kv_layers(kv):
+    """The device array of layer base pointers v3d_beam_kv_gather walks (built once per allocation): kv = per-layer tensors
+    [n_slices, rows, width]."""
+    return torch.tensor([k.data_ptr() for k in kv], dtype=torch.int64).to(kv[0].device)
+
+
+def beam_kv_gather(kv, layer_ptrs, S, n, src_base, dst_base, parents, done=None):
+    """For every layer: rows [S, S + n) of slice src_base + parents[b] -> slice dst_base + b, b < len(parents), one launch
+    (v3d_beam_kv_gather).  kv: the per-layer [n_slices, rows, width] 16-bit tensors layer_ptrs was built from."""
+    k0 = kv[0]
+    if k0.dim() != 3 or k0.stride(2) != 1 or k0.element_size() != 2 or layer_ptrs.numel() != len(kv) or parents.dtype != torch.int32:
+        raise V3DError(f"beam_kv_gather: kv {tuple(k0.shape)}")
+    check(lib().v3d_beam_kv_gather(_p(layer_ptrs), len(kv), k0.stride(0), k0.stride(1), k0.shape[2], k0.shape[0], k0.shape[1], int(S), int(n), int(src_base),
+                                   int(dst_base), parents.numel(), _p(parents), _p(done), _stream()), "v3d_beam_kv_gather")
+
+
 # ------------------------------------------------------------------------------ grounding
 
 
