@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define V3D_ABI_VERSION 7   /* 2: *_rows decode entries, fp8 path, a7 / a3 device entries; 3: rope_kv_store, add_row, ...; 4: resize_bicubic, eos_update, embed_grad bounds; 6: sumsq, *_rows entries take 1..32 rows; 7: attention_shared_prefix; ground_scores_rows, add_rows and the v3d_beam_* entries were ADDED under 7 (no entry changed) */
+#define V3D_ABI_VERSION 7   /* 2: *_rows decode entries, fp8 path, a7 / a3 device entries; 3: rope_kv_store, add_row, ...; 4: resize_bicubic, eos_update, embed_grad bounds; 6: sumsq, *_rows entries take 1..32 rows; 7: attention_shared_prefix; ground_scores_rows, add_rows and the v3d_beam_* entries were ADDED under 7 (no entry changed); so were the v3d_sample_* entries */
 
 enum { V3D_F32 = 0, V3D_F16 = 1, V3D_BF16 = 2 };
 enum { V3D_U8_HWC = 16 };   /* v3d_resize_bicubic_u8 only: 8-bit interleaved output, no normalisation */
@@ -415,6 +415,27 @@ int v3d_beam_step_host(const float* cand_score, const int32_t* cand_flat, int K,
 int v3d_beam_kv_gather(void* const* layer_ptrs, int n_layers, int64_t slice_stride, int64_t row_stride, int width, int n_slices,
                        int64_t slice_rows, int S, int n, int src_base, int dst_base, int B, const int32_t* parents, const int32_t* done,
                        void* stream);
+
+/* ------------------------------------------------------------------ sampling (do_sample) - */
+/* Added under ABI 7 (no entry changed).  The rule is DESIGN section 2, "Sampling, stated once": transformers' temperature, top-k
+ * and top-p warpers (min_tokens_to_keep = 1; top_k == 0 and top_p == 1 mean "off"), ties ordered by the lower index, then one
+ * Gumbel-max draw per row from Philox4x32-10 at counter (token >> 2, step, stream, 0), key = seed.
+ *
+ * v3d_sample_rows: M <= 32 rows of 16-bit logits x + m * ldx, V columns, M * V < 2^31.  streams: device int32[M], the rows'
+ * stream ids, or NULL for 0 .. M-1.  out_index: device int64[M].  kept (device int32[M], may be NULL): the size of each row's kept
+ * set.  A row's token depends on its logits, seed, step and stream only.  workspace: v3d_sample_workspace_bytes(M, V), 16-byte
+ * aligned.  v3d_sample_chunk: the vocab columns one workgroup of the draw covers (a row is cut at its multiples).
+ * v3d_sample_rows_host: the same rule over f32 logits in host memory (the integer parts are the kernel's bits; the mass of the
+ * top-p test is summed in f64 and the keys use the host's logf). */
+int64_t v3d_sample_workspace_bytes(int M, int V);
+int v3d_sample_chunk(int M, int V);
+int v3d_sample_rows(const void* logits, int64_t ldx, int M, int V, int dtype, float temperature, int top_k, float top_p, uint64_t seed,
+                    int step, const int32_t* streams, int64_t* out_index, int32_t* kept, void* workspace, int64_t workspace_bytes,
+                    void* stream);
+int v3d_sample_rows_host(const float* logits, int64_t ldx, int M, int V, float temperature, int top_k, float top_p, uint64_t seed,
+                         int step, const int32_t* streams, int64_t* out_index, int32_t* kept);
+/* Philox4x32-10 as the sampler uses it (counter[4], key[2] -> out[4]): the known-answer hook of the tests. */
+int v3d_philox4x32_10_host(const uint32_t* counter, const uint32_t* key, uint32_t* out);
 
 /* ------------------------------------------------------------------ grounding (K19, K20) - */
 

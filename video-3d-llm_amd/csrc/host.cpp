@@ -1,5 +1,5 @@
 // Host side of the C ABI: error reporting and the host-only helpers (frame sampling,
-// greedy max-coverage frame selection, the beam-search step's twin).
+// greedy max-coverage frame selection, the beam-search step's twin, the sampler's twin).
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -10,6 +10,7 @@
 
 #include "v3d.h"
 #include "beam_step.h"
+#include "sample_rule.h"
 
 namespace v3d {
 
@@ -144,5 +145,62 @@ extern "C" int v3d_beam_step_host(const float* cand_score, const int32_t* cand_f
   const v3d::BeamView s = v3d::beam_view((int32_t*)state, B, max_new_tokens);
   if (v3d::beam_step_decide(s, B, K, V, max_new_tokens, step, cand_score, cand_flat, eos_ids, n_eos, div, next_tokens, parents, trace_score, trace_flat))
     v3d::beam_step_move(s, B, V, max_new_tokens, step, cand_flat, 0, 1);
+  return V3D_OK;
+}
+
+// do_sample: the twin of v3d_sample_rows over f32 logits - the rule of DESIGN section 2 "Sampling, stated once" by a plain sort.
+// Philox words, u and the top-k cut are the kernel's bits (sample_rule.h); the top-p mass is summed in f64, keys use this side's logf.
+extern "C" int v3d_sample_rows_host(const float* logits, int64_t ldx, int M, int V, float temperature, int top_k, float top_p, uint64_t seed,
+                                    int step, const int32_t* streams, int64_t* out_index, int32_t* kept) {
+  if (!logits || !out_index) {
+    v3d::set_error("v3d_sample_rows_host: null pointer");
+    return V3D_E_INVALID;
+  }
+  if (!v3d::sample_args_ok(M, V, temperature, top_k, top_p) || step < 0 || (M > 1 && ldx < V)) {
+    v3d::set_error("v3d_sample_rows_host: bad arguments (M=%d V=%d ldx=%lld T=%g top_k=%d top_p=%g step=%d)", M, V, (long long)ldx, (double)temperature,
+                   top_k, (double)top_p, step);
+    return V3D_E_INVALID;
+  }
+  std::vector<int32_t> order((size_t)V);
+  for (int m = 0; m < M; ++m) {
+    const float* x = logits + (int64_t)m * ldx;
+    const uint32_t stream = streams ? (uint32_t)streams[m] : (uint32_t)m;
+    for (int i = 0; i < V; ++i) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [x](int32_t a, int32_t b) { return x[a] > x[b]; });   // value descending, index ascending
+    int n = v3d::sample_top_k(top_k, V);
+    if (top_p < 1.f) {
+      const float zmax = v3d::sample_scaled(x[order[0]], temperature);
+      double Z = 0.0;
+      for (int r = 0; r < n; ++r) Z += std::exp((double)(v3d::sample_scaled(x[order[(size_t)r]], temperature) - zmax));
+      double before = 0.0;
+      int keep = 0;
+      for (int r = 0; r < n; ++r) {
+        if (!(r == 0 || before / Z < (double)top_p)) break;
+        ++keep;
+        before += std::exp((double)(v3d::sample_scaled(x[order[(size_t)r]], temperature) - zmax));
+      }
+      n = keep;
+    }
+    float best = 0.f;
+    int32_t best_i = -1;
+    for (int r = 0; r < n; ++r) {
+      const int32_t i = order[(size_t)r];
+      const v3d::Philox4 w = v3d::sample_words((uint32_t)i >> 2, (uint32_t)step, stream, seed);
+      const float key = v3d::sample_key(x[i], temperature, w.w[i & 3]);
+      if (best_i < 0 || key > best || (key == best && i < best_i)) { best = key; best_i = i; }
+    }
+    out_index[m] = best_i;
+    if (kept) kept[m] = n;
+  }
+  return V3D_OK;
+}
+
+extern "C" int v3d_philox4x32_10_host(const uint32_t* counter, const uint32_t* key, uint32_t* out) {
+  if (!counter || !key || !out) {
+    v3d::set_error("v3d_philox4x32_10_host: null pointer");
+    return V3D_E_INVALID;
+  }
+  const v3d::Philox4 w = v3d::philox4x32_10(counter[0], counter[1], counter[2], counter[3], key[0], key[1]);
+  for (int i = 0; i < 4; ++i) out[i] = w.w[i];
   return V3D_OK;
 }

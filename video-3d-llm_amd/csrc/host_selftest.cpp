@@ -121,6 +121,42 @@ int main() {
     CHECK(v3d_beam_step_host(sc[0], fl[0], K, B, V, L, L, eos, 1, div, st.data(), next, par, ts.data(), tf.data()) == V3D_E_INVALID);
     CHECK(v3d_beam_step_host(nullptr, fl[0], K, B, V, L, 0, eos, 1, div, st.data(), next, par, ts.data(), tf.data()) == V3D_E_INVALID);
   }
+  // do_sample: Philox known answers, the sampler's twin on a ragged shape, its degenerate forms and its argument check
+  {
+    const uint32_t c0[4] = {0, 0, 0, 0}, k0[2] = {0, 0}, c1[4] = {~0u, ~0u, ~0u, ~0u}, k1[2] = {~0u, ~0u};
+    const uint32_t c2[4] = {0x243f6a88u, 0x85a308d3u, 0x13198a2eu, 0x03707344u}, k2[2] = {0xa4093822u, 0x299f31d0u};
+    uint32_t o[4];
+    CHECK(v3d_philox4x32_10_host(c0, k0, o) == V3D_OK && o[0] == 0x6627e8d5u && o[1] == 0xe169c58du && o[2] == 0xbc57ac4cu && o[3] == 0x9b00dbd8u);
+    CHECK(v3d_philox4x32_10_host(c1, k1, o) == V3D_OK && o[0] == 0x408f276du && o[1] == 0x41c83b0eu && o[2] == 0xa20bc7c6u && o[3] == 0x6d5451fdu);
+    CHECK(v3d_philox4x32_10_host(c2, k2, o) == V3D_OK && o[0] == 0xd16cfe09u && o[1] == 0x94fdccebu && o[2] == 0x5001e420u && o[3] == 0x24126ea1u);
+    CHECK(v3d_philox4x32_10_host(nullptr, k0, o) == V3D_E_INVALID);
+    const int M = 3, V = 37, ldx = 41;
+    std::vector<float> x((size_t)M * ldx);
+    for (auto& v : x) v = (float)(std::rand() % 17) * 0.25f;                 // many equal values
+    std::vector<int64_t> tok(M, -1), top(M, -1);
+    std::vector<int32_t> kept(M, -1);
+    const int32_t streams[M] = {5, 6, 7};
+    for (int step = 0; step < 50; ++step) {
+      CHECK(v3d_sample_rows_host(x.data(), ldx, M, V, 0.7f, 5, 0.9f, 1234567890123ull, step, streams, tok.data(), kept.data()) == V3D_OK);
+      for (int m = 0; m < M; ++m) CHECK(tok[m] >= 0 && tok[m] < V && kept[m] >= 1 && kept[m] <= 5);
+      CHECK(v3d_sample_rows_host(x.data(), ldx, M, V, 1.0f, 0, 1.0f, 7, step, nullptr, tok.data(), kept.data()) == V3D_OK);
+      for (int m = 0; m < M; ++m) CHECK(tok[m] >= 0 && tok[m] < V && kept[m] == V);
+      CHECK(v3d_sample_rows_host(x.data(), ldx, M, V, 1.0f, 1, 1.0f, 7, step, nullptr, top.data(), nullptr) == V3D_OK);
+      CHECK(v3d_sample_rows_host(x.data(), ldx, M, V, 1.0f, 0, 1e-6f, 7, step, nullptr, tok.data(), kept.data()) == V3D_OK);
+      for (int m = 0; m < M; ++m) {                                          // both are the first maximum of the row
+        int best = 0;
+        for (int i = 1; i < V; ++i) if (x[(size_t)m * ldx + i] > x[(size_t)m * ldx + best]) best = i;
+        CHECK(top[m] == best && tok[m] == best && kept[m] == 1);
+      }
+    }
+    CHECK(v3d_sample_rows_host(x.data(), ldx, M, V, 0.f, 0, 1.f, 0, 0, nullptr, tok.data(), nullptr) == V3D_E_INVALID);
+    CHECK(v3d_sample_rows_host(x.data(), ldx, M, V, 1.f, -1, 1.f, 0, 0, nullptr, tok.data(), nullptr) == V3D_E_INVALID);
+    CHECK(v3d_sample_rows_host(x.data(), ldx, M, V, 1.f, 0, 0.f, 0, 0, nullptr, tok.data(), nullptr) == V3D_E_INVALID);
+    CHECK(v3d_sample_rows_host(x.data(), ldx, M, V, 1.f, 0, 1.5f, 0, 0, nullptr, tok.data(), nullptr) == V3D_E_INVALID);
+    CHECK(v3d_sample_rows_host(x.data(), ldx, 33, V, 1.f, 0, 1.f, 0, 0, nullptr, tok.data(), nullptr) == V3D_E_INVALID);
+    CHECK(v3d_sample_rows_host(x.data(), V - 1, M, V, 1.f, 0, 1.f, 0, 0, nullptr, tok.data(), nullptr) == V3D_E_INVALID);
+    CHECK(v3d_sample_rows_host(nullptr, ldx, M, V, 1.f, 0, 1.f, 0, 0, nullptr, tok.data(), nullptr) == V3D_E_INVALID);
+  }
   std::puts("host_selftest ok");
   return 0;
 }

@@ -15,11 +15,13 @@ v3d.engine.Engine's HBM layouts.  Call contracts mirrored (3-D eval drivers):
                                                                                          -> (None, scores [n_obj + 1])
     model(input_ids, images=..., modalities="video", video_dict=..., [labels=...])       -> CausalLMOutputWithPast(loss, logits [1,S,V] f32)
 generate is greedy only, no autograd (the loss is a forward value); sampling / beams / box_labels raise NotImplementedError there, unknown keyword
-arguments raise TypeError - nothing is silently dropped.  Beam search has its own entry, model.generate_beam(..., num_beams=N, length_penalty=p):
+arguments raise TypeError - nothing is silently dropped.  Sampling has its own entry, model.generate_sample(..., temperature=T, top_p=p,
+top_k=k, seed=s) (the device sampler, seeded).  Beam search has its own entry, model.generate_beam(..., num_beams=N, length_penalty=p):
 generate's arguments and return.
 """
 import json
 import os
+import types
 import warnings
 
 import torch
@@ -79,6 +81,7 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
         tower = SigLipVisionTower(getattr(config, "mm_vision_tower", "siglip"), vision_tower_cfg=config).bind(self.engine)
         self.model = LlavaQwenModel(config, self.engine, tower)
         self.generation_eos = None
+        self.generation_config = None                  # the checkpoint's generation_config.json, when it ships one (from_pretrained)
 
     # ------------------------------------------------------------------ loading (builder.py:206-228)
     @classmethod
@@ -124,7 +127,9 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
         gen = os.path.join(path, "generation_config.json")
         if os.path.exists(gen):
             with open(gen) as f:
-                model.generation_eos = json.load(f).get("eos_token_id")
+                shipped = json.load(f)
+            model.generation_eos = shipped.get("eos_token_id")
+            model.generation_config = types.SimpleNamespace(**shipped)      # generate_sample's defaults (temperature, top_k, top_p)
         return model.eval()
 
     def resize_token_embeddings(self, new_num_tokens=None, **kw):
@@ -224,7 +229,8 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
             raise TypeError(f"LlavaQwenForCausalLM.generate: unsupported arguments {sorted(unknown)} (accepted: {sorted(self._GENERATE_KW)})")
         if kwargs.get("do_sample") or (kwargs.get("num_beams") or 1) != 1:
             raise NotImplementedError("greedy decoding only (the 3-D eval drivers run temperature 0, num_beams 1); beam search is "
-                                      "generate_beam(input_ids, images=..., video_dict=..., num_beams=N)")
+                                      "generate_beam(input_ids, images=..., video_dict=..., num_beams=N), sampling is "
+                                      "generate_sample(input_ids, images=..., video_dict=..., temperature=T, top_p=p, top_k=k, seed=s)")
         return self._generate(inputs, images, kwargs)
 
     @torch.no_grad()
@@ -240,8 +246,35 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
             raise NotImplementedError("stopping_criteria cannot be combined with beams: they stop by EOS ids and max_new_tokens only")
         return self._generate(inputs, images, kwargs, num_beams=int(num_beams), length_penalty=float(length_penalty))
 
-    def _generate(self, inputs, images, kwargs, num_beams=1, length_penalty=1.0):
-        """The argument handling generate and generate_beam share, then Engine.generate."""
+    @torch.no_grad()
+    def generate_sample(self, inputs=None, images=None, image_sizes=None, modalities=("image",), temperature=None, top_p=None, top_k=None, seed=None,
+                        stream=0, **kwargs):
+        """generate(...) with do_sample=True (Engine's sampler: transformers' temperature, top-k and top-p warpers and one seeded draw per
+        token on the device; DESIGN section 2, "Sampling, stated once"): the same arguments, the same [1, n_new] return.  temperature /
+        top_k / top_p left as None fall back to self.generation_config, as transformers does (a missing or None entry: 1.0 / 0 / 1.0).
+        seed=None draws one 63-bit seed from torch's default CPU generator, so torch.manual_seed makes a run reproducible; the random
+        stream itself is the project's own (Philox4x32-10), not torch's.  stream: the id of this prompt's random stream under the seed (the eval
+        runners pass the question's index, so a record does not depend on how questions are batched)."""
+        unknown = set(kwargs) - self._GENERATE_KW
+        if unknown:
+            raise TypeError(f"LlavaQwenForCausalLM.generate_sample: unsupported arguments {sorted(unknown)} (accepted: {sorted(self._GENERATE_KW)})")
+        if kwargs.get("do_sample") is False:
+            raise NotImplementedError("generate_sample samples (do_sample=True); greedy decoding is generate()")
+        if (kwargs.get("num_beams") or 1) != 1:
+            raise NotImplementedError("beam-sample is not built: generate_sample draws one sequence (num_beams=1)")
+        gc = getattr(self, "generation_config", None)
+
+        def pick(given, name, default):
+            v = given if given is not None else getattr(gc, name, None)
+            return default if v is None else v
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        sampling = dict(do_sample=True, temperature=float(pick(temperature, "temperature", 1.0)), top_k=int(pick(top_k, "top_k", 0)),
+                        top_p=float(pick(top_p, "top_p", 1.0)), seed=int(seed), stream=int(stream))
+        return self._generate(inputs, images, kwargs, sampling=sampling)
+
+    def _generate(self, inputs, images, kwargs, num_beams=1, length_penalty=1.0, sampling=None):
+        """The argument handling generate, generate_beam and generate_sample share, then Engine.generate."""
         if kwargs.get("use_cache") is False:
             raise NotImplementedError("use_cache=False: the engine always decodes through its KV cache")
         am = kwargs.get("attention_mask")
@@ -270,7 +303,7 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
         beams = dict(num_beams=num_beams, length_penalty=length_penalty) if num_beams > 1 else {}
         out = self.engine.generate(ids, frames, coords, max_new_tokens=max_new, eos_token_id=self._eos(kwargs.get("eos_token_id")),
                                    stopping=stopping, box_input=box_input if box_input is not None and len(box_input) else None,
-                                   coord_token_id=coord_ids[0] if coord_ids else None, **beams)
+                                   coord_token_id=coord_ids[0] if coord_ids else None, **beams, **(sampling or {}))
         return out.view(1, -1)
 
     def prepare_inputs_for_generation(self, *a, **kw):

@@ -32,6 +32,7 @@ c_p = ctypes.c_void_p
 c_i = ctypes.c_int
 c_l = ctypes.c_int64
 c_f = ctypes.c_float
+c_u64 = ctypes.c_uint64
 
 # name -> (restype, argtypes); mirrors include/v3d.h one to one
 SIGNATURES = {
@@ -137,6 +138,11 @@ SIGNATURES = {
     "v3d_beam_step": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "v3d_beam_step_host": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "v3d_beam_kv_gather": (c_i, [c_p, c_i, c_l, c_l, c_i, c_i, c_l, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
+    "v3d_sample_workspace_bytes": (c_l, [c_i, c_i]),
+    "v3d_sample_chunk": (c_i, [c_i, c_i]),
+    "v3d_sample_rows": (c_i, [c_p, c_l, c_i, c_i, c_i, c_f, c_i, c_f, c_u64, c_i, c_p, c_p, c_p, c_p, c_l, c_p]),
+    "v3d_sample_rows_host": (c_i, [c_p, c_l, c_i, c_i, c_f, c_i, c_f, c_u64, c_i, c_p, c_p, c_p]),
+    "v3d_philox4x32_10_host": (c_i, [c_p, c_p, c_p]),
 }
 
 

@@ -720,14 +720,18 @@ class Engine:
     # ------------------------------------------------------------------ generate (a23)
     @torch.no_grad()
     def generate(self, input_ids, images, world_coords, max_new_tokens=16, eos_token_id=None, stopping=None, box_input=None,
-                 coord_token_id=None, num_beams=1, length_penalty=1.0, return_trace=False):
+                 coord_token_id=None, num_beams=1, length_penalty=1.0, return_trace=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, stream=0,
+                 return_logits=False):
         """Greedy decoding of one (scene, question): LlavaQwenForCausalLM.generate (llava_qwen.py:208-236)
         with do_sample=False, num_beams=1 as model_scanqa.py:173-185 calls it.  eos_token_id: an int or a collection of ints;
         stopping: optional host callback(token_ids_so_far: LongTensor [n]) -> bool, checked after every token (HF's
         stopping_criteria; forces one host synchronisation per step).
         num_beams > 1 (the drivers' --num_beams): the same prefill, then beam_search (length_penalty, return_trace: see there);
-        stopping callbacks cannot be combined with beams."""
+        stopping callbacks cannot be combined with beams.
+        do_sample: every token is drawn on the device instead (_sampler: temperature, top_k, top_p, seed, stream; return_logits).  Not
+        with num_beams > 1."""
         self._check_beams(num_beams, stopping, return_trace)
+        sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, [stream], num_beams, return_logits)
         feats = self.encode_images(images)
         ids = self.voxel_ids(world_coords.to(self.dtype))
         x = self.build_inputs_embeds(input_ids, feats, ids, box_input=box_input, coord_token_id=coord_token_id)
@@ -736,7 +740,35 @@ class Engine:
         logits = self.llm_forward(x, 0, last_rows=[S - 1])
         if num_beams > 1:
             return self.beam_search(logits, S, num_beams, max_new_tokens, eos_token_id, length_penalty, return_trace)
-        return self.decode_loop(logits, S, max_new_tokens, eos_token_id, stopping)
+        return self.decode_loop(logits, S, max_new_tokens, eos_token_id, stopping, sampler=sampler)
+
+    def _sampler(self, do_sample, temperature, top_k, top_p, seed, streams, num_beams=1, return_logits=False):
+        """The sampling arguments of one generation call, checked once: None for do_sample=False (the greedy code runs untouched), else
+        the rule's arguments ("Sampling, stated once"), the rows' stream ids on the device and the engine's one
+        sampling workspace.  Token n of a row is drawn at step n (0 = from the prefill logits) of the row's stream, so a row's tokens
+        depend on its logits, the seed and its stream id only - not on the rows it is batched with.  return_logits: the call also
+        returns the [n_steps, M, V] logits every token was chosen from."""
+        if not do_sample:
+            if return_logits:
+                raise V3DError("return_logits belongs to do_sample=True")
+            return None
+        if num_beams != 1:
+            raise V3DError("do_sample cannot be combined with num_beams > 1: beam-sample is not built")
+        T, p = float(temperature), float(top_p)
+        if not (T > 0.0 and math.isfinite(T)) or not (0.0 < p <= 1.0) or int(top_k) != top_k or top_k < 0:
+            raise V3DError(f"do_sample needs a finite temperature > 0, top_k >= 0 and 0 < top_p <= 1 (got {temperature!r}, {top_k!r}, {top_p!r})")
+        streams = [int(v) for v in streams]
+        if any(not 0 <= v < (1 << 31) for v in streams):
+            raise V3DError("a sampling stream id is an integer in [0, 2^31)")
+        sp = SceneContext()
+        sp.T, sp.top_k, sp.top_p, sp.seed = T, int(top_k), p, int(seed) & 0xFFFFFFFFFFFFFFFF
+        sp.streams = torch.tensor(streams, dtype=torch.int32).to(self.device)
+        ws = self.__dict__.get("_sample_ws")
+        if ws is None or ws[0] != self.cfg.llm.vocab:                              # (the vocabulary can grow: grow_vocab)
+            ws = self._sample_ws = (self.cfg.llm.vocab, ops.sample_workspace(self.MAX_GROUP, self.cfg.llm.vocab, self.device))
+        ws = ws[1]
+        sp.ws, sp.return_logits, sp.logits = ws, bool(return_logits), None
+        return sp
 
     @staticmethod
     def _check_beams(num_beams, stopping, return_trace=False):
@@ -779,15 +811,17 @@ class Engine:
 
     @torch.no_grad()
     def answer(self, question_ids, max_new_tokens=16, eos_token_id=None, stopping=None, num_beams=1, length_penalty=1.0, return_trace=False,
-               box_input=None, coord_token_id=None):
+               box_input=None, coord_token_id=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, stream=0, return_logits=False):
         """Greedy answer to one question about the scene prefilled by prefill_scene: only the question's rows (the ids that follow
         the prefix in the full prompt) run through the decoder, at positions P.., attending to the cached prefix; then the
         usual decode loop.  Causality makes the prefix rows of the uncached pass independent of the question, so the tokens are
         those of generate(prefix_ids + question_ids, ...) (tests/test_gpu_scene_reuse.py).  The prefix rows are left intact.
         num_beams > 1: beam_search behind the same question rows, as generate does.
         box_input [x, y, z] + coord_token_id (Scan2Cap): the PE of the discretised box centre on the question's <coord> rows, as
-        build_inputs_embeds adds it for a whole prompt."""
+        build_inputs_embeds adds it for a whole prompt.
+        do_sample: as generate (stream: this question's stream id, the one answer_group would give it)."""
         self._check_beams(num_beams, stopping, return_trace)
+        sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, [stream], num_beams, return_logits)
         P = getattr(self.ctx, "prefix_len", 0)
         if not P or self.ctx.kv_len < P:
             raise V3DError("answer() needs prefill_scene() on this context first")
@@ -808,7 +842,7 @@ class Engine:
         logits = self.llm_forward(x, P, last_rows=[Q - 1])
         if num_beams > 1:
             return self.beam_search(logits, P + Q, num_beams, max_new_tokens, eos_token_id, length_penalty, return_trace)
-        return self.decode_loop(logits, P + Q, max_new_tokens, eos_token_id, stopping)
+        return self.decode_loop(logits, P + Q, max_new_tokens, eos_token_id, stopping, sampler=sampler)
 
     MAX_GROUP = 32          # scenes / questions whose decode steps share a pass over the weights (r04: 32; csrc DEC_MAX_ROWS)
 
@@ -915,13 +949,17 @@ class Engine:
         return scene, st, x, P, lens, Sq, share
 
     @torch.no_grad()
-    def answer_group(self, questions, max_new_tokens=16, eos_token_id=None, box_inputs=None, coord_token_id=None):
+    def answer_group(self, questions, max_new_tokens=16, eos_token_id=None, box_inputs=None, coord_token_id=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+                     streams=None, return_logits=False):
         """Up to 32 questions about the scene prefilled by prefill_scene, answered together: the cached prefix K/V is handed to
         each question's own cache (one broadcast copy per layer), the questions' rows run through the decoder as ONE batch
         (one pass over the weights; rows padded to the longest question, which causality keeps from affecting the real rows),
         then all answers decode as one group (decode_group).  Returns a list of token-id tensors, each cut after its first EOS.
         A question's rows do not depend on the others (tests/test_gpu_scene_reuse.py: equal to answer() on it alone).
-        box_inputs / coord_token_id (Scan2Cap): question_embeds - each question's box-centre PE on its <coord> rows."""
+        box_inputs / coord_token_id (Scan2Cap): question_embeds - each question's box-centre PE on its <coord> rows.
+        do_sample: every row draws from its own stream (streams: one id per question, default its index), so a question's answer is
+        the one answer(..., stream=id) draws; with return_logits the result is (answers, logits [n_steps, G, V])."""
+        sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, self._streams(streams, len(questions)), 1, return_logits)
         scene, st, x, P, lens, Sq, share = self._question_rows("answer_group", questions, max_new_tokens, box_inputs, coord_token_id)
         G, l = len(questions), self.cfg.llm
         last = torch.tensor([g * Sq + lens[g] - 1 for g in range(G)], dtype=torch.int64, device=self.device)
@@ -936,9 +974,16 @@ class Engine:
         for c, n in zip(ctxs, lens):
             c.kv_len = P + n
         toks = self.decode_group(rows, ctxs, [P + n for n in lens], max_new_tokens, logits_ready=True, shared_prefix=P if share else 0,
-                                 eos_token_id=eos_token_id, prefix_kv=scene.kv if share else None)
+                                 eos_token_id=eos_token_id, prefix_kv=scene.kv if share else None, sampler=sampler)
         self.use(scene)
-        return [r.to(self.device) for r in self.trim_at_eos(toks, eos_token_id)]
+        out = [r.to(self.device) for r in self.trim_at_eos(toks, eos_token_id)]
+        return (out, sampler.logits) if return_logits else out
+
+    def _streams(self, streams, n):
+        streams = list(range(n)) if streams is None else list(streams)
+        if len(streams) != n:
+            raise V3DError(f"streams: one sampling stream id per row ({len(streams)} for {n} rows)")
+        return streams
 
     @torch.no_grad()
     def ground_group(self, questions, ground_rows):
@@ -969,13 +1014,15 @@ class Engine:
         return torch.stack([self.ground_head(query[g: g + 1], scene.ground_of) for g in range(G)])
 
     @torch.no_grad()
-    def generate_group(self, samples, max_new_tokens=16, eos_token_id=None):
+    def generate_group(self, samples, max_new_tokens=16, eos_token_id=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, streams=None, return_logits=False):
         """Throughput form of `generate` for up to 32 (input_ids, images, world_coords) samples: each is prefilled into its
         own context, then all decode together (one pass over the weights per step).  Returns a list of token-id tensors,
-        each cut after its first EOS like `generate` does.  The contexts and the row buffers are cached on the engine."""
+        each cut after its first EOS like `generate` does.  The contexts and the row buffers are cached on the engine.
+        do_sample: as answer_group (streams: one id per sample, default its index)."""
         n = len(samples)
         if not 1 <= n <= self.MAX_GROUP:
             raise V3DError(f"generate_group takes 1 to {self.MAX_GROUP} samples")
+        sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, self._streams(streams, n), 1, return_logits)
         pool = self.__dict__.setdefault("_group_ctxs", [])
         while len(pool) < n:
             pool.append(self.new_context())
@@ -995,8 +1042,9 @@ class Engine:
                 lens.append(x.shape[0])
         finally:
             self.use(keep)
-        toks = self.decode_group(grp, pool[:n], lens, max_new_tokens, eos_token_id=eos_token_id)
-        return [r.to(self.device) for r in self.trim_at_eos(toks, eos_token_id)]
+        toks = self.decode_group(grp, pool[:n], lens, max_new_tokens, eos_token_id=eos_token_id, sampler=sampler)
+        out = [r.to(self.device) for r in self.trim_at_eos(toks, eos_token_id)]
+        return (out, sampler.logits) if return_logits else out
 
     # ------------------------------------------------------------------ scenes decoding together
     def new_group(self, n_scenes):
@@ -1064,18 +1112,28 @@ class Engine:
             ops.linear_decode_rows(g.last[:M], self.l_head, g.logits[:M])
         return g.logits[:M, : l.vocab]
 
-    def decode_group(self, g, ctxs, prompt_lens, max_new_tokens, logits_ready=False, shared_prefix=0, eos_token_id=None, lookahead=2, prefix_kv=None):
+    def decode_group(self, g, ctxs, prompt_lens, max_new_tokens, logits_ready=False, shared_prefix=0, eos_token_id=None, lookahead=2, prefix_kv=None,
+                     do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, streams=None, return_logits=False, sampler=None):
         """Greedy decoding of M prefilled scenes together (their prefill logits are in ctx.logits[0], or already in g.logits
         with logits_ready); returns the token ids [M, n_steps] (device), n_steps <= max_new_tokens.
         eos_token_id (int or ints): the stop test runs on the device (v3d_eos_update: a done mask per row and their count); the
         host reads the count through a pinned copy `lookahead` steps behind the step it is queueing, so the launch queue never
         drains and the group stops at most `lookahead` - 1 steps after its last row has produced an EOS.  Rows that finished
         earlier keep decoding (their columns are independent); callers cut every row after its first EOS (trim_at_eos).
-        Without eos_token_id all max_new_tokens steps run."""
+        Without eos_token_id all max_new_tokens steps run.
+        do_sample (or a sampler built by _sampler): ops.sample_rows stands where ops.argmax_rows does, step counted from 0, row m on
+        streams[m] (default m); nothing else in the loop changes.  With return_logits the logits of the executed steps are left in
+        sampler.logits [n_steps, M, V] (and returned beside the tokens when this method built the sampler)."""
         l = self.cfg.llm
         M = len(ctxs)
         if M > g.n:
             raise V3DError("decode group too small")
+        own = sampler is None and do_sample
+        if own:
+            sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, self._streams(streams, M), 1, return_logits)
+        if sampler is not None and sampler.streams.numel() != M:
+            raise V3DError("decode_group: one sampling stream id per row")
+        keep = torch.empty((max_new_tokens, M, l.vocab), dtype=self.dtype, device=self.device) if sampler is not None and sampler.return_logits else None
         self._check_room(max(prompt_lens), max_new_tokens)
         toks = torch.empty((max_new_tokens, M), dtype=torch.int64, device=self.device)
         if not logits_ready:
@@ -1088,7 +1146,12 @@ class Engine:
             st.done[:M].zero_()
         n_steps = max_new_tokens
         for step in range(max_new_tokens):
-            ops.argmax_rows(logits, toks[step], g.amax_ws)
+            if sampler is None:
+                ops.argmax_rows(logits, toks[step], g.amax_ws)
+            else:
+                if keep is not None:
+                    keep[step].copy_(logits)
+                ops.sample_rows(logits, toks[step], sampler.ws, sampler.T, sampler.top_k, sampler.top_p, sampler.seed, step, sampler.streams)
             if eos:
                 ops.eos_update(toks[step], st.eos, st.done[:M], st.n_done)
                 st.host[step].copy_(st.n_done, non_blocking=True)
@@ -1103,6 +1166,10 @@ class Engine:
                 break
             ops.embed_gather(self.embed, toks[step], out=g.x[:M])
             logits = self.decode_forward_rows(g, ctxs, [S + step for S in prompt_lens], shared_prefix=shared_prefix, prefix_kv=prefix_kv)
+        if keep is not None:
+            sampler.logits = keep[:n_steps]
+            if own:
+                return toks[:n_steps].t(), sampler.logits
         return toks[:n_steps].t()
 
     def _eos_state(self, g, eos, max_new_tokens):
@@ -1131,11 +1198,19 @@ class Engine:
             out.append(row)
         return out
 
-    def decode_loop(self, logits, S, max_new_tokens, eos_token_id=None, stopping=None, lookahead=2):
+    def decode_loop(self, logits, S, max_new_tokens, eos_token_id=None, stopping=None, lookahead=2, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, stream=0,
+                    return_logits=False, sampler=None):
         """Greedy loop of one scene; token ids stay on the device (argmax kernel -> embedding gather).  EOS: the stop test runs on
         the device and the host reads it `lookahead` - 1 steps late (as decode_group does), so the launch queue never drains; the
-        returned ids end with the first EOS.  A stopping callback (HF stopping_criteria) forces one host synchronisation per step."""
+        returned ids end with the first EOS.  A stopping callback (HF stopping_criteria) forces one host synchronisation per step.
+        do_sample (or a sampler built by _sampler): ops.sample_rows stands where ops.argmax does, step counted from 0 on `stream`;
+        with return_logits the result is (ids, logits [n, 1, V])."""
         self._check_room(S, max_new_tokens)
+        if sampler is None and do_sample:
+            sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, [stream], 1, return_logits)
+        keep = None
+        if sampler is not None and sampler.return_logits:
+            keep = torch.empty((max_new_tokens, 1, self.cfg.llm.vocab), dtype=self.dtype, device=self.device)
         eos = () if eos_token_id is None else ((int(eos_token_id),) if isinstance(eos_token_id, int) else tuple(int(e) for e in eos_token_id))
         toks = torch.empty(max_new_tokens, dtype=torch.int64, device=self.device)
         st = None
@@ -1144,7 +1219,13 @@ class Engine:
             st.done[:1].zero_()
         n = 0
         for step in range(max_new_tokens):
-            ops.argmax(logits, toks[step: step + 1])
+            if sampler is None:
+                ops.argmax(logits, toks[step: step + 1])
+            else:
+                row = logits.reshape(1, -1)[:, : self.cfg.llm.vocab]
+                if keep is not None:
+                    keep[step].copy_(row)
+                ops.sample_rows(row, toks[step: step + 1], sampler.ws, sampler.T, sampler.top_k, sampler.top_p, sampler.seed, step, sampler.streams)
             n = step + 1
             if st is not None:
                 ops.eos_update(toks[step: step + 1], st.eos, st.done[:1], st.n_done)
@@ -1166,6 +1247,9 @@ class Engine:
         out = toks[:n]
         if st is not None:
             out = self.trim_at_eos(out[None], eos)[0].to(self.device)
+        if keep is not None:
+            sampler.logits = keep[: out.numel()]
+            return out, sampler.logits
         return out
 
     # ------------------------------------------------------------------ beam search (a23, num_beams > 1)

@@ -165,7 +165,7 @@ def default_workers():
 
 def model_answer_fn(model, tokenizer, image_processor, video_processor, model_name, max_frame_num=32, max_new_tokens=512,
                     reuse_scenes=False, times=None, pipeline=True, group_size=16, workers=None, stats=None, record_fn=None, pool=None,
-                    box_input_fn=None, skip_fn=None, num_beams=1, length_penalty=1.0):
+                    box_input_fn=None, skip_fn=None, num_beams=1, length_penalty=1.0, sampling=None, stream_fn=None):
     """The per-rank loop of model_scanqa.py:130-206 around `model` (the loader-produced LlavaQwenForCausalLM).
     reuse_scenes: one scene prefill per run of consecutive questions about a scene (pipelined or, with pipeline=False, synchronous).
     pipeline (default): v3d.pipeline - asynchronous host loader, prefill / grouped-decode overlap, device-side stop test; the
@@ -177,7 +177,15 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
     <coord> token rows); skip_fn(line) -> True: the question is not run and its answer is "" (:199-200).
     num_beams > 1 (the drivers' --num_beams; length_penalty with it): beam search per question - the plain one-question loop calling
     model.generate_beam, or with reuse_scenes one scene prefill and Engine.answer(num_beams=N) per question.  The pipeline's cross-scene
-    decode group and answer_group's batches are greedy and are not used with beams."""
+    decode group and answer_group's batches are greedy and are not used with beams.
+    sampling = dict(temperature, top_k, top_p, seed) (the drivers' --temperature > 0): every token is drawn by the device sampler -
+    model.generate_sample per question, or with reuse_scenes one scene prefill and Engine.answer_group(do_sample=True) per batch.
+    stream_fn(line) -> the question's sampling stream id (its index in the question file), so a record does not depend on batching,
+    on reuse_scenes or on the number of ranks.  Not with num_beams > 1."""
+    if sampling and num_beams > 1:
+        raise ValueError("sampling (temperature > 0) cannot be combined with num_beams > 1: beam-sample is not built")
+    if sampling and stream_fn is None:
+        raise ValueError("sampling needs stream_fn: each question's stream id (its index in the question file)")
     record_fn = record_fn or (lambda line, text: make_record(line, text, model_name))
     coord_ids = getattr(getattr(model, "config", None), "coord_token_ids", None)
 
@@ -201,7 +209,10 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
                                            box_input=box_input_fn(line) if box_input_fn else None)
                 t0 = time.time()
                 with torch.inference_mode():
-                    if num_beams > 1:
+                    if sampling:
+                        toks = model.generate_sample(ids, images=images, modalities="video", num_beams=1, max_new_tokens=max_new_tokens,
+                                                     use_cache=True, video_dict=vd, stream=stream_fn(line), **sampling)
+                    elif num_beams > 1:
                         toks = model.generate_beam(ids, images=images, modalities="video", do_sample=False, temperature=0.0, top_p=None,
                                                    num_beams=num_beams, length_penalty=length_penalty, max_new_tokens=max_new_tokens,
                                                    use_cache=True, video_dict=vd)
@@ -250,8 +261,9 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
                                                   num_beams=num_beams, length_penalty=length_penalty,
                                                   box_input=None if boxes is None else boxes[k], coord_token_id=coord_id)) for k, q in enumerate(qs)]
                         continue
+                    draw = dict(do_sample=True, streams=[stream_fn(l) for l in lines[b: b + len(qs)]], **sampling) if sampling else {}
                     answers = eng.answer_group(qs, max_new_tokens=min(max_new_tokens, room), eos_token_id=eos, box_inputs=boxes,
-                                               coord_token_id=coord_id)
+                                               coord_token_id=coord_id, **draw)
                     out += [decode(a) for a in answers]
             i = j
         return out
@@ -356,7 +368,7 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
                           "wall_seconds": time.time() - t0})
         return [decode(t) for scene_answers in answers for t in scene_answers]
 
-    if num_beams > 1:
+    if num_beams > 1 or sampling:
         return scene_batches if reuse_scenes else one_by_one
     if reuse_scenes:
         return scene_pipelined if pipeline else scene_batches
@@ -364,6 +376,29 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
 
 
 LLM_WEIGHTS = ("bf16", "fp8", "fp4")
+
+
+def add_sampling_arguments(ap):
+    ap.add_argument("--temperature", type=float, default=0.0,
+                    help="the reference drivers' flag: 0 (default) decodes greedily; > 0 draws every token on the device from softmax(logits / "
+                         "temperature) after --top_k and --top_p (do_sample = temperature > 0).  Each question draws from its own random stream, "
+                         "numbered by its index in the question file, so the records do not depend on batching, --reuse-scenes or the number "
+                         "of ranks; sampling runs one question (or, with --reuse-scenes, one scene's batch) at a time")
+    ap.add_argument("--top_p", type=float, default=1.0, help="sampling: keep the most probable tokens whose mass before them is below top_p (1: off)")
+    ap.add_argument("--top_k", type=int, default=0, help="sampling: keep the top_k most probable tokens (0: off)")
+    ap.add_argument("--seed", type=int, default=0, help="sampling: the 64-bit seed of the run")
+
+
+def sampling_arguments(ap, a, questions=None):
+    """(sampling, stream_fn) of model_answer_fn from the parsed flags: (None, None) at temperature 0."""
+    if a.temperature < 0 or not 0.0 < a.top_p <= 1.0 or a.top_k < 0:
+        ap.error("--temperature >= 0, 0 < --top_p <= 1, --top_k >= 0")
+    if a.temperature == 0:
+        return None, None
+    if a.num_beams > 1:
+        ap.error("--temperature > 0 cannot be combined with --num_beams > 1: beam-sample is not built")
+    index = {id(q): i for i, q in enumerate(questions or [])}
+    return dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed), (lambda line: index[id(line)])
 
 
 def add_beam_arguments(ap):
@@ -421,7 +456,9 @@ def main(argv=None):
     ap.add_argument("--n_gpu", type=int, default=None,
                     help="the reference's flag (model_scanqa.py:222): started plainly with N > 1, launch N ranks of this runner on this node")
     add_beam_arguments(ap)
+    add_sampling_arguments(ap)
     a = ap.parse_args(argv)
+    sampling_arguments(ap, a)
     if os.path.exists(a.answer_file):                                                         # model_scanqa.py:238-240
         print(f"The {a.answer_file} already exists!!!")
         return 0
@@ -431,7 +468,8 @@ def main(argv=None):
     with open(os.path.expanduser(a.question_file)) as f:
         questions = json.load(f)[: a.test_size]
     pool = None
-    if not a.no_pipeline and a.loader_workers >= 0 and a.num_beams == 1:
+    sampling, stream_fn = sampling_arguments(ap, a, questions)
+    if not a.no_pipeline and a.loader_workers >= 0 and a.num_beams == 1 and not sampling:
         from . import frame_io
         pool = frame_io.make_pool(a.loader_workers or default_workers())        # forked before this process touches the GPU
     rank, world, dev, gather_dev = rank_setup(a.n_gpu)
@@ -442,7 +480,7 @@ def main(argv=None):
     times = []
     fn = model_answer_fn(model, tokenizer, image_processor, vp, name, a.max_frame_num, a.max_new_tokens, a.reuse_scenes, times,
                          pipeline=not a.no_pipeline, group_size=a.decode_group, workers=(0 if a.loader_workers < 0 else a.loader_workers or None), pool=pool,
-                         num_beams=a.num_beams, length_penalty=a.length_penalty)
+                         num_beams=a.num_beams, length_penalty=a.length_penalty, sampling=sampling, stream_fn=stream_fn)
     records = evaluate(questions, fn, rank, world, gather_dev, shard=a.shard or ("scene" if a.reuse_scenes else "stride"))
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(a.answer_file)), exist_ok=True)

@@ -852,6 +852,68 @@ def beam_kv_gather(kv, layer_ptrs, S, n, src_base, dst_base, parents, done=None)
                                    int(dst_base), parents.numel(), _p(parents), _p(done), _stream()), "v3d_beam_kv_gather")
 
 
+# ------------------------------------------------------------------------------ sampling (csrc/sample.hip, csrc/sample_rule.h)
+
+SAMPLE_MAX_M = 32
+
+
+def sample_chunk(M, V):
+    """The vocab columns one workgroup of v3d_sample_rows' draw covers: a row of V logits is cut at the multiples of this."""
+    return int(lib().v3d_sample_chunk(int(M), int(V)))
+
+
+def sample_workspace(M, V, device="cuda"):
+    """Device scratch of v3d_sample_rows for up to M rows of V logits (v3d_sample_workspace_bytes)."""
+    need = int(lib().v3d_sample_workspace_bytes(int(M), int(V)))
+    if need <= 0:
+        raise V3DError(f"sample_workspace: 1 to {SAMPLE_MAX_M} rows and M * V < 2^31 (M={M} V={V})")
+    return torch.empty((need + 3) // 4, dtype=torch.int32, device=device)
+
+
+def sample_rows(logits, out, workspace, temperature=1.0, top_k=0, top_p=1.0, seed=0, step=0, streams=None, kept=None, V=None):
+    """logits [M, >=V] 16-bit rows -> out int64 [M]: one token per row drawn from softmax(logits / temperature) after top-k and top-p
+    ("Sampling, stated once"; v3d_sample_rows).  seed: 64 bits; step: 0 for the token drawn from the prefill logits,
+    then 1, 2, ...; streams: device int32 [M], the rows' stream ids (None: 0 .. M-1); kept (optional device int32 [M]): the size of each
+    row's kept set.  A row's token depends on its logits, seed, step and stream only."""
+    x = logits if logits.dim() == 2 else logits[None]
+    M = x.shape[0]
+    V = x.shape[1] if V is None else int(V)
+    if x.stride(1) != 1 or x.shape[1] < V or out.dtype != torch.int64 or out.numel() < M or not out.is_contiguous():
+        raise V3DError(f"sample_rows: logits {tuple(x.shape)}, out {tuple(out.shape)} {out.dtype}")
+    if streams is not None and (streams.dtype != torch.int32 or streams.numel() < M or not streams.is_contiguous() or not streams.is_cuda):
+        raise V3DError("sample_rows: streams is a contiguous device int32 [M]")
+    if kept is not None and (kept.dtype != torch.int32 or kept.numel() < M or not kept.is_contiguous() or not kept.is_cuda):
+        raise V3DError("sample_rows: kept is a contiguous device int32 [M]")
+    check(lib().v3d_sample_rows(_p(x), x.stride(0), M, V, _code(x), float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                int(step), _p(streams), _p(out), _p(kept), _p(workspace), workspace.numel() * workspace.element_size(), _stream()),
+          "v3d_sample_rows")
+    return out
+
+
+def sample_rows_host(logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, step=0, streams=None):
+    """The host twin (v3d_sample_rows_host): logits f32 [M, V] (host) -> (tokens int64 [M], kept int32 [M])."""
+    x = logits if logits.dim() == 2 else logits[None]
+    if x.is_cuda or x.dtype != torch.float32 or x.stride(1) != 1:
+        raise V3DError("sample_rows_host: host f32 rows")
+    M, V = x.shape
+    tok, kept = torch.zeros(M, dtype=torch.int64), torch.zeros(M, dtype=torch.int32)
+    st = None if streams is None else torch.as_tensor(streams, dtype=torch.int32).contiguous()
+    if st is not None and st.numel() < M:
+        raise V3DError("sample_rows_host: one stream id per row")
+    check(lib().v3d_sample_rows_host(_p(x), x.stride(0), M, V, float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step),
+                                     _p(st), _p(tok), _p(kept)), "v3d_sample_rows_host")
+    return tok, kept
+
+
+def philox4x32_10_host(counter, key):
+    """Philox4x32-10 as the sampler uses it: counter (4 words), key (2 words) -> 4 words (v3d_philox4x32_10_host)."""
+    c = torch.tensor([int(v) for v in counter], dtype=torch.int64).to(torch.int32)
+    k = torch.tensor([int(v) for v in key], dtype=torch.int64).to(torch.int32)
+    o = torch.zeros(4, dtype=torch.int32)
+    check(lib().v3d_philox4x32_10_host(_p(c), _p(k), _p(o)), "v3d_philox4x32_10_host")
+    return [int(v) & 0xFFFFFFFF for v in o.tolist()]
+
+
 # ------------------------------------------------------------------------------ grounding
 
 
