@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define V3D_ABI_VERSION 7   /* 2: *_rows decode entries, fp8 path, a7 / a3 device entries; 3: rope_kv_store, add_row, ...; 4: resize_bicubic, eos_update, embed_grad bounds; 6: sumsq, *_rows entries take 1..32 rows; 7: attention_shared_prefix; ground_scores_rows, add_rows and the v3d_beam_* entries were ADDED under 7 (no entry changed); so were the v3d_sample_* entries */
+#define V3D_ABI_VERSION 7   /* 2: *_rows decode entries, fp8 path, a7 / a3 device entries; 3: rope_kv_store, add_row, ...; 4: resize_bicubic, eos_update, embed_grad bounds; 6: sumsq, *_rows entries take 1..32 rows; 7: attention_shared_prefix; ground_scores_rows, add_rows and the v3d_beam_* entries were ADDED under 7 (no entry changed); so were the v3d_sample_* entries, and v3d_coord_points_voxel, v3d_sin3d_table_points_layout, v3d_sin3d_table_build_points, v3d_sin3d_pe_points and v3d_visual_tokens_points */
 
 enum { V3D_F32 = 0, V3D_F16 = 1, V3D_BF16 = 2 };
 enum { V3D_U8_HWC = 16 };   /* v3d_resize_bicubic_u8 only: 8-bit interleaved output, no normalisation */
@@ -133,6 +133,57 @@ enum { V3D_VT_POOL = 1, V3D_VT_PE = 2, V3D_VT_NEWLINE = 4 };
 int v3d_visual_tokens(const void* feat, const int32_t* ids, const void* table, int n_ids,
                       const void* newline, void* out, int64_t out_stride, int dtype, int V, int side,
                       int n, int C, int flags, void* stream);
+
+/* ------------------------------------------------- the other position encodings (P points) ---- */
+
+/* llava_arch.py:225-257 `sample_n_points` / `minmax_coordinate_in_patch` followed by :259-272 `discrete_coords`: the
+ * world_position_embedding_type variants other than `avg` (which stays on v3d_coord_pool_voxel).
+ * coords [V,S,S,3] (dtype); S must be 384 and patch 27 (the reference hard-codes a 14 x 27 grid, :245), n = 14.
+ *   SAMPLE9  pixel (27*py + {4,13,22}, 27*px + {4,13,22}) of every patch, point index 3*ri + ci      P = 9
+ *   SAMPLE5  points 0, 2, 4, 6, 8 of those                                                            P = 5
+ *   SAMPLE1  point 4 of those                                                                         P = 1
+ *   MINMAX   point 0 the per-axis minimum over the 27x27 patch, point 1 the maximum; a NaN in the patch gives NaN  P = 2
+ * Outputs (any may be NULL), all [V,n,n,P,3]: pts dtype (exact copies of input values); vox dtype (integer-valued,
+ * what `discrete_coords` returns); ids int32.  The sample modes read P pixels per patch, never the frame; MINMAX
+ * reads the first 378 rows once (coords 16-byte aligned).  min_xyz_host / max_xyz_host: 3 floats each on the HOST. */
+enum { V3D_PTS_SAMPLE9 = 0, V3D_PTS_SAMPLE5 = 1, V3D_PTS_SAMPLE1 = 2, V3D_PTS_MINMAX = 3 };
+int v3d_coord_points_voxel(const void* coords, int dtype, int V, int S, int patch, int mode,
+                           const float* min_xyz_host, const float* max_xyz_host, float voxel_size,
+                           void* pts, void* vox, int32_t* ids, void* stream);
+
+/* Layout of the PE table for PositionEmbeddingSine3D(embedding_size, n_points) (position_encoding.py:17-49):
+ * num_feats = embedding_size / (3*n_points) must be at least 16/sizeof(dtype).  Segment q (point q/3, axis q%3) of a
+ * token row starts (q*num_feats) % (16/sizeof) elements past a 16-byte boundary; the table keeps one copy of the
+ * [n_ids, num_feats] values per DISTINCT such shift.  Returns the number of copies (1..16/sizeof), or a negative
+ * error; writes the elements of one row to *row_elems_host and copy c's shift to shifts_host[c] (host pointers,
+ * either may be NULL; shifts_host holds up to 8 entries). */
+int v3d_sin3d_table_points_layout(int embedding_size, int n_points, int dtype, int64_t* row_elems_host,
+                                  int32_t* shifts_host);
+
+/* The table itself: table [n_copies][n_ids][row_elems] dtype, copy c holding T(PE value) of id at elements
+ * shift_c .. shift_c + num_feats - 1 of its row and zero bits elsewhere.  dim_t [num_feats] f32 from the caller, as for
+ * v3d_sin3d_table_build. */
+int v3d_sin3d_table_build_points(const float* dim_t, int embedding_size, int n_points, int n_ids, int dtype,
+                                 void* table, void* stream);
+
+/* PositionEmbeddingSine3D(embedding_size, n_points).forward for arbitrary coordinates: xyz [N,n_points,3] dtype ->
+ * out [N,embedding_size] dtype.  Channel c < 3*n_points*num_feats: q = c / num_feats, j = c % num_feats,
+ * sin (j even) or cos (j odd) of xyz[q] / dim_t[j]; f32 IEEE division, correctly rounded trig, one cast to dtype; the
+ * remaining channels are 0.  Box centres and object centres are encoded with the centre repeated n_points times
+ * (llava_arch.py:409-413). */
+int v3d_sin3d_pe_points(const void* xyz, int dtype, int64_t N, int n_points, const float* dim_t,
+                        int embedding_size, void* out, void* stream);
+
+/* v3d_visual_tokens with n_points points per token (flags POOL, NEWLINE as there; PE is required).  The PE operand is
+ *   ids [V, n*n, n_points, 3] int32 + table from v3d_sin3d_table_build_points for (C, n_points, dtype)   (default), or
+ *   pts [V, n*n, n_points, 3] dtype + dim_t [C/(3*n_points)] f32, trig evaluated per channel (flag CONTINUOUS: a type
+ *   without `discrete`, llava_arch.py:509-512; serves `avg-sin3d` with n_points = 1 too).
+ * The unused pair may be NULL.  Same rounding points as v3d_visual_tokens; with n_points = 1 and ids the output equals
+ * v3d_visual_tokens bit for bit, and with integer-valued pts the CONTINUOUS form equals the table form. */
+enum { V3D_VT_CONTINUOUS = 8 };
+int v3d_visual_tokens_points(const void* feat, const int32_t* ids, const void* pts, const void* table, int n_ids,
+                             const float* dim_t, int n_points, const void* newline, void* out, int64_t out_stride,
+                             int dtype, int V, int side, int n, int C, int flags, void* stream);
 
 /* K9  embed_tokens gather for the text segments (llava_arch.py:693): out[i,:] = table[ids[i],:]. */
 int v3d_embed_gather(const void* table, int64_t vocab, int C, const int64_t* ids, int64_t n,

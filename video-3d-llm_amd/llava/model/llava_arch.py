@@ -1,10 +1,11 @@
 """llava.model.llava_arch on the HIP engine (reference: llava/model/llava_arch.py).
 
 `LlavaMetaModel` / `LlavaMetaForCausalLM` keep the reference's names, method signatures and return conventions for the
-video + `avg-discrete-sin3d` + bilinear-pool + `grid`-newline branch - the one every 3-D eval driver and the shipped
-training script select (scripts/3d/train/train_multi.sh:78-87) - and launch kernels of libv3d_hip.so through
-v3d.engine.Engine.  Branches those scripts never reach (anyres / unpad image grids, faster-video, mrope, llava3d,
-sample9 / minmax / mlp PE, multi-image prompts, batch > 1) raise NotImplementedError instead of computing something else.
+video + sin3d position encoding + bilinear-pool + `grid`-newline branch - `avg-discrete-sin3d` is the one every 3-D eval
+driver and the shipped training script select (scripts/3d/train/train_multi.sh:78-87); the paper's other sin3d types
+(avg / sample9 / sample5 / sample1 / minmax, with or without `discrete`) run for inference - and launch kernels of
+libv3d_hip.so through v3d.engine.Engine.  Branches those scripts never reach (anyres / unpad image grids, faster-video,
+mrope, llava3d, mlp PE, multi-image prompts, batch > 1) raise NotImplementedError instead of computing something else.
 """
 import math
 
@@ -42,7 +43,8 @@ class LlavaMetaModel:
         self.vision_tower = vision_tower
         self.mm_projector = _Projector(engine)
         self.image_newline = engine.newline
-        self.world_position_embedding = PositionEmbeddingSine3D(config.hidden_size)
+        # llava_arch.py:51-63: the module is built for the type's number of points
+        self.world_position_embedding = PositionEmbeddingSine3D(config.hidden_size, n_points=engine.cfg.n_points)
 
     def get_vision_tower(self):
         return self.vision_tower
@@ -75,6 +77,23 @@ class LlavaMetaForCausalLM:
                                          self.config.voxel_size, want_vox=False, want_ids=False)
         return avg
 
+    # ---- llava_arch.py:225-239
+    def minmax_coordinate_in_patch(self, world_coords, patch_size=27):
+        """[V,384,384,3] -> [V,14,14,2,3]: per-axis minimum and maximum over each patch."""
+        return self._coord_points(world_coords, "minmax", patch_size)
+
+    # ---- llava_arch.py:241-257
+    def sample_n_points(self, world_coords, n_points=9):
+        """[V,384,384,3] -> [V,14,14,n_points,3] ([V,14,14,3] for n_points = 1): pixels 4, 13, 22 of each patch's rows and columns."""
+        if n_points not in (9, 5, 1):
+            raise NotImplementedError
+        return self._coord_points(world_coords, f"sample{n_points}", 27)
+
+    def _coord_points(self, world_coords, mode, patch_size):
+        c = self.config
+        return ops.coord_points_voxel(world_coords, mode, patch_size, c.min_xyz_range, c.max_xyz_range, c.voxel_size, want_vox=False,
+                                      want_ids=False)[0]
+
     # ---- llava_arch.py:259-272
     def discrete_coords(self, world_coords, xyz_min=None):
         """clamp / shift / divide / round, integer-valued floats of the input dtype."""
@@ -93,13 +112,24 @@ class LlavaMetaForCausalLM:
 
     def fused_visual_tokens(self, image_feature, world_coords, table, out=None):
         """The whole 3-D branch for one video sample in two launches (llava_arch.py:395-420, 469, 506-517, 536):
-        coords [F,384,384,3] -> voxel ids;  feat [F,729,C] -> pooled + PE(ids) + newline rows [F*210, C]."""
+        coords [F,384,384,3] -> voxel ids;  feat [F,729,C] -> pooled + PE(ids) + newline rows [F*210, C].  The aggregation, the number
+        of points and `discrete` follow config.world_position_embedding_type; `table` is a Sin3DTable for that number of points
+        (unused, may be None, for a type without `discrete`)."""
+        from v3d.loader import parse_position_type
         c = self.config
-        _, _, ids = ops.coord_pool_voxel(world_coords, 27, c.min_xyz_range, c.max_xyz_range, c.voxel_size,
-                                         want_avg=False, want_vox=False)
+        aggregation, n_points, discrete = parse_position_type(getattr(c, "world_position_embedding_type", "avg-discrete-sin3d"))
         side = self.get_vision_tower().num_patches_per_side
-        return ops.visual_tokens(image_feature, ids, table, self.get_model().image_newline, side=side,
-                                 n=math.ceil(side / 2), pool=True, out=out)
+        if aggregation == "avg":
+            pts, _, ids = ops.coord_pool_voxel(world_coords, 27, c.min_xyz_range, c.max_xyz_range, c.voxel_size,
+                                               want_avg=not discrete, want_vox=False, want_ids=discrete)
+        else:
+            pts, _, ids = ops.coord_points_voxel(world_coords, aggregation, 27, c.min_xyz_range, c.max_xyz_range, c.voxel_size,
+                                                 want_pts=not discrete, want_vox=False, want_ids=discrete)
+        if discrete:
+            return ops.visual_tokens(image_feature, ids, table, self.get_model().image_newline, side=side,
+                                     n=math.ceil(side / 2), pool=True, out=out, n_points=n_points)
+        return ops.visual_tokens(image_feature, newline=self.get_model().image_newline, side=side, n=math.ceil(side / 2), pool=True,
+                                 out=out, n_points=n_points, pts=pts)
 
     # ---- llava_arch.py:336-836
     def prepare_inputs_labels_for_multimodal(self, input_ids, position_ids, attention_mask, past_key_values, labels, images,
@@ -118,7 +148,7 @@ class LlavaMetaForCausalLM:
             raise NotImplementedError("the accelerated path takes one video sample per call (batch 1, modalities=['video']), "
                                       "as every 3-D eval driver passes")
         if video_dict is None or "world_coords" not in video_dict:
-            raise ValueError("video_dict['world_coords'] is required (world_position_embedding_type 'avg-discrete-sin3d')")
+            raise ValueError("video_dict['world_coords'] is required (every sin3d world_position_embedding_type takes its PE from them)")
         if past_key_values is not None:
             raise NotImplementedError("an external past_key_values cache is not supported: the engine owns the KV cache")
         if attention_mask is not None and not bool(attention_mask.bool().all()):

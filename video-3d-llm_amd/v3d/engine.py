@@ -59,6 +59,11 @@ class EngineConfig:
     voxel_size: float = 0.1
     ground_head_type: str = "infonce"      # llava_qwen.py:57-104: 'infonce' (the shipped checkpoints), 'mlp', 'score'
     object_feature_type: str = "patch14-pe"  # llava_arch.py:367-376: 'patch14-*' (ViT patches) or 'patch27-*' (pooled tokens)
+    # world_position_embedding_type, parsed by loader.parse_position_type (llava_arch.py:395-420): how a patch's coordinates are
+    # aggregated, how many points that gives, and whether they are voxelised before the PE.  The default is the shipped type.
+    aggregation: str = "avg"               # 'avg' | 'sample9' | 'sample5' | 'sample1' | 'minmax'
+    n_points: int = 1                      # 1 | 9 | 5 | 1 | 2
+    discrete: bool = True
 
 
 def random_state_dict(cfg: EngineConfig, dtype, device, seed=0, std=0.02, ground_head=False):
@@ -185,7 +190,11 @@ class Engine:
         self.embed = sd["model.embed_tokens.weight"].contiguous()
         n_ids = int(round((max(cfg.max_xyz[0] - cfg.min_xyz[0], cfg.max_xyz[1] - cfg.min_xyz[1],
                                cfg.max_xyz[2] - cfg.min_xyz[2])) / cfg.voxel_size)) + 1
-        self.pe_table = ops.Sin3DTable(l.hidden, n_ids, dtype, device)
+        if {"avg": 1, **{k: p for k, (_, p) in ops.POINT_MODES.items()}}.get(cfg.aggregation) != cfg.n_points:
+            raise V3DError(f"aggregation {cfg.aggregation!r} with n_points {cfg.n_points}: see loader.parse_position_type")
+        # PE values per voxel id for the configured number of points; a type without `discrete` evaluates the trig per token instead
+        self.pe_table = ops.Sin3DTable(l.hidden, n_ids, dtype, device, n_points=cfg.n_points) if cfg.discrete else None
+        self._pe_dim_t = None if cfg.discrete else ops.reference_dim_t(l.hidden // (3 * cfg.n_points)).to(device)
         self.rope = ops.RopeTable(self.hd, l.max_pos, l.rope_theta, dtype, device)
         self._alloc(max_frames)
 
@@ -395,11 +404,33 @@ class Engine:
         return self.v_x[: n_frames * n, : self.cfg.vit.hidden].reshape(n_frames, n, -1)
 
     # ------------------------------------------------------------------ fusion (a11-a17)
+    @property
+    def pe_dim_t(self):
+        return self.pe_table.dim_t if self.pe_table is not None else self._pe_dim_t
+
     def voxel_ids(self, world_coords):
-        """[F,384,384,3] (model dtype) -> int32 [F,14,14,3]   (llava_arch.py:403, 416)."""
+        """[F,384,384,3] (model dtype) -> int32 [F,14,14,3]   (llava_arch.py:403, 416).  For the other types (llava_arch.py:395-420):
+        [F,14,14,P,3] with P points per patch ([F,14,14,3] for sample1), int32 voxel ids when the type is `discrete`, else the
+        aggregated coordinates themselves in the model dtype - whichever build_inputs_embeds takes the PE of."""
         c = self.cfg
-        _, _, ids = ops.coord_pool_voxel(world_coords, 27, c.min_xyz, c.max_xyz, c.voxel_size, want_avg=False, want_vox=False)
-        return ids
+        if c.aggregation == "avg" and c.discrete:
+            _, _, ids = ops.coord_pool_voxel(world_coords, 27, c.min_xyz, c.max_xyz, c.voxel_size, want_avg=False, want_vox=False)
+            return ids
+        if c.aggregation == "avg":
+            return ops.coord_pool_voxel(world_coords, 27, c.min_xyz, c.max_xyz, c.voxel_size, want_vox=False, want_ids=False)[0]
+        pts, _, ids = ops.coord_points_voxel(world_coords, c.aggregation, 27, c.min_xyz, c.max_xyz, c.voxel_size, want_pts=not c.discrete,
+                                             want_vox=False, want_ids=c.discrete)
+        return ids if c.discrete else pts
+
+    def centre_pe(self, centres):
+        """PE rows [N, hidden] of box / object centres [N,3] (model dtype, on the device): voxelised when the type is `discrete`, the
+        centre repeated n_points times (llava_arch.py:409-420), then the same module as the visual tokens'."""
+        c = self.cfg
+        if c.discrete:
+            centres = ops.discrete_coords(centres, c.min_xyz, c.max_xyz, c.voxel_size)
+        if c.n_points > 1:
+            centres = centres[:, None, :].expand(-1, c.n_points, -1).contiguous()
+        return ops.sin3d_pe(centres[None], c.llm.hidden, dim_t=self.pe_dim_t, n_points=c.n_points)[0]
 
     def build_inputs_embeds(self, input_ids, feats, ids, image_token=-200, box_input=None, coord_token_id=None, stamp=None):
         """prepare_inputs_labels_for_multimodal for one video sample (llava_arch.py:336-836, eval branch):
@@ -423,7 +454,12 @@ class Engine:
         up = lambda t: (t if t.is_cuda else t.pin_memory().to(self.device, non_blocking=True))      # noqa: E731  (no host-blocking pageable copy)
         if len(pre):
             ops.embed_gather(self.embed, up(pre), out=x[: len(pre)])
-        vt = lambda: ops.visual_tokens(feats, ids, self.pe_table, self.newline, side=side, n=n, pool=True, out=x[len(pre): len(pre) + n_vis])      # noqa: E731
+        if self.cfg.discrete:
+            vt = lambda: ops.visual_tokens(feats, ids, self.pe_table, self.newline, side=side, n=n, pool=True, out=x[len(pre): len(pre) + n_vis],      # noqa: E731
+                                           n_points=self.cfg.n_points)
+        else:       # `ids` holds the aggregated coordinates (voxel_ids): trig per token
+            vt = lambda: ops.visual_tokens(feats, newline=self.newline, side=side, n=n, pool=True, out=x[len(pre): len(pre) + n_vis],      # noqa: E731
+                                           n_points=self.cfg.n_points, pts=ids, dim_t=self.pe_dim_t)
         if stamp is not None:
             stamp(vt)             # bench: HIP events around the north-star kernel
         else:
@@ -433,10 +469,7 @@ class Engine:
         if coord_token_id is not None and box_input is not None and len(box_input):
             rows = [r if r < at else r + n_vis - 1 for r, t in enumerate(ids_list) if t == coord_token_id]
             if rows:
-                c = self.cfg
-                centre = ops.discrete_coords(box_input.to(device=self.device, dtype=self.dtype).reshape(-1, 3)[:1].contiguous(),
-                                             c.min_xyz, c.max_xyz, c.voxel_size)
-                pe = ops.sin3d_pe(centre[None], c.llm.hidden, dim_t=self.pe_table.dim_t)[0, 0]
+                pe = self.centre_pe(box_input.to(device=self.device, dtype=self.dtype).reshape(-1, 3)[:1].contiguous())[0]
                 ops.add_row(x, torch.tensor(rows, dtype=torch.int64, device=self.device), pe)
         return x
 
@@ -708,8 +741,7 @@ class Engine:
         (27 x 27 cells of 14 pixels, >= 98 of 196 inside); 'patch27': the POOLED tokens before the PE (14 x 14 cells of 27 pixels,
         >= 182 of 729).  feats [F,729,H] (encode_images), coords [F,384,384,3] and boxes [n,6] in the model dtype -> [n, H]."""
         H = self.cfg.llm.hidden
-        centres = ops.discrete_coords(boxes[:, :3].contiguous(), self.cfg.min_xyz, self.cfg.max_xyz, self.cfg.voxel_size)
-        pe = ops.sin3d_pe(centres[None], H, dim_t=self.pe_table.dim_t)[0]
+        pe = self.centre_pe(boxes[:, :3].contiguous())
         if "patch27" in self.cfg.object_feature_type:
             mask = ops.object_patch_mask(coords, boxes, cell=27, thresh=int(27 * 27 * 0.25))
             rows = ops.visual_tokens(feats, side=27, n=self.cfg.pool_out, pool=True)          # get_2dPool alone: [F, 196, H]
@@ -834,10 +866,7 @@ class Engine:
         if coord_token_id is not None and box_input is not None and len(box_input):
             rows = [r for r, t in enumerate(question_ids.tolist()) if t == coord_token_id]
             if rows:
-                c = self.cfg
-                centre = ops.discrete_coords(torch.as_tensor(box_input, dtype=torch.float32).to(device=self.device, dtype=self.dtype).reshape(-1, 3)[:1].contiguous(),
-                                             c.min_xyz, c.max_xyz, c.voxel_size)
-                pe = ops.sin3d_pe(centre[None], c.llm.hidden, dim_t=self.pe_table.dim_t)[0, 0]
+                pe = self.centre_pe(torch.as_tensor(box_input, dtype=torch.float32).to(device=self.device, dtype=self.dtype).reshape(-1, 3)[:1].contiguous())[0]
                 ops.add_row(x, torch.tensor(rows, dtype=torch.int64, device=self.device), pe)
         logits = self.llm_forward(x, P, last_rows=[Q - 1])
         if num_beams > 1:
@@ -901,10 +930,7 @@ class Engine:
                     src += [len(centres)] * len(hit)
                     centres.append([float(v) for v in torch.as_tensor(box, dtype=torch.float32).reshape(-1)[:3]])
             if rows:
-                c = self.cfg
-                centre = ops.discrete_coords(torch.tensor(centres, dtype=torch.float32).to(device=self.device, dtype=self.dtype),
-                                             c.min_xyz, c.max_xyz, c.voxel_size)
-                pe = ops.sin3d_pe(centre[None], c.llm.hidden, dim_t=self.pe_table.dim_t)[0]
+                pe = self.centre_pe(torch.tensor(centres, dtype=torch.float32).to(device=self.device, dtype=self.dtype))
                 ops.add_rows(x, rows, src, pe)
         return x
 

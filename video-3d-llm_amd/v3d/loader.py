@@ -58,15 +58,27 @@ def read_tower_weights(tower_dir):
     return out
 
 
+def parse_position_type(wtype):
+    """world_position_embedding_type -> (aggregation, n_points, discrete), with the reference's precedence (llava_arch.py:395-407,
+    :51-58): the first of avg / sample9 / sample5 / sample1 / minmax the string contains; `discrete` = voxelise before the PE; `sin3d`
+    is the only PE on the accelerated path (`mlp` needs checkpoint weights, `mrope` another rotary rule: DESIGN section 2)."""
+    if "mrope" in wtype or "mlp" in wtype:
+        raise V3DError(f"world_position_embedding_type {wtype!r}: the 'mlp' and 'mrope' encodings are not on the accelerated path")
+    if "sin3d" not in wtype:
+        raise V3DError(f"world_position_embedding_type {wtype!r}: only 'sin3d' encodings are on the accelerated path")
+    for aggregation, n_points in (("avg", 1), ("sample9", 9), ("sample5", 5), ("sample1", 1), ("minmax", 2)):
+        if aggregation in wtype:
+            return aggregation, n_points, "discrete" in wtype
+    raise V3DError(f"world_position_embedding_type {wtype!r} names none of avg / sample9 / sample5 / sample1 / minmax")
+
+
 def engine_config(hf_config, sd, max_positions=None):
     """EngineConfig from the HF config (Qwen2 fields, llava_qwen.py:37-38 + the 3-D keys train_3d.py:1429-1459 persists)
     and the SigLIP tensors' shapes.  The tower keeps every layer the checkpoint has except the one the reference deletes
     (siglip_encoder.py:570): a checkpoint saved AFTER that deletion (the tower was trained / saved with the model) has it
     gone already, a raw SigLIP directory still has all 27."""
     c = hf_config
-    wtype = getattr(c, "world_position_embedding_type", "avg-discrete-sin3d")
-    if not all(t in wtype for t in ("avg", "discrete", "sin3d")) or "mrope" in wtype or "mlp" in wtype:
-        raise V3DError(f"world_position_embedding_type {wtype!r}: only the shipped 'avg-discrete-sin3d' variant is on the accelerated path")
+    aggregation, n_points, discrete = parse_position_type(getattr(c, "world_position_embedding_type", "avg-discrete-sin3d"))
     for key, want in (("mm_spatial_pool_mode", "bilinear"), ("mm_newline_position", "grid"), ("mm_projector_type", "mlp2x_gelu")):
         got = getattr(c, key, want)
         if got != want:
@@ -90,7 +102,8 @@ def engine_config(hf_config, sd, max_positions=None):
     return EngineConfig(vit=vit, llm=llm, min_xyz=tuple(getattr(c, "min_xyz_range", (-15, -15, -5))),
                         max_xyz=tuple(getattr(c, "max_xyz_range", (15, 15, 5))), voxel_size=float(getattr(c, "voxel_size", 0.1)),
                         ground_head_type=getattr(c, "ground_head_type", None) or "infonce",
-                        object_feature_type=getattr(c, "object_feature_type", None) or "patch14-pe")
+                        object_feature_type=getattr(c, "object_feature_type", None) or "patch14-pe",
+                        aggregation=aggregation, n_points=n_points, discrete=discrete)
 
 
 def drop_deleted_tower_layer(sd, tower_from_raw_siglip):

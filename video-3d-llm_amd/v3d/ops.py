@@ -11,7 +11,7 @@ from ._native import V3DError, check, lib
 F32, F16, BF16 = 0, 1, 2
 _DT = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 
-VT_POOL, VT_PE, VT_NEWLINE = 1, 2, 4
+VT_POOL, VT_PE, VT_NEWLINE, VT_CONTINUOUS = 1, 2, 4, 8
 
 
 def _code(t):
@@ -137,6 +137,35 @@ def coord_pool_voxel(coords, patch=27, min_xyz=(-15, -15, -5), max_xyz=(15, 15, 
     return avg, vox, ids
 
 
+PTS_SAMPLE9, PTS_SAMPLE5, PTS_SAMPLE1, PTS_MINMAX = 0, 1, 2, 3
+POINT_MODES = {"sample9": (PTS_SAMPLE9, 9), "sample5": (PTS_SAMPLE5, 5), "sample1": (PTS_SAMPLE1, 1), "minmax": (PTS_MINMAX, 2)}
+
+
+def coord_points_voxel(coords, mode, patch=27, min_xyz=(-15, -15, -5), max_xyz=(15, 15, 5), voxel_size=0.1,
+                       want_pts=True, want_vox=True, want_ids=True):
+    """sample_n_points / minmax_coordinate_in_patch (+ discrete_coords).  coords [V,384,384,3], mode 'sample9' | 'sample5' |
+    'sample1' | 'minmax' (or its PTS_* code) -> (pts, vox [V,14,14,P,3] same dtype, ids int32); 'sample1' gives [V,14,14,3] as the
+    reference does.  'avg' is coord_pool_voxel."""
+    x = _dev(coords, "coords")
+    if x.dim() != 4 or x.shape[1] != x.shape[2] or x.shape[3] != 3:
+        raise V3DError(f"coords must be [V,S,S,3], got {tuple(x.shape)}")
+    V, S = x.shape[0], x.shape[1]
+    if mode in POINT_MODES:
+        code, P = POINT_MODES[mode]
+    elif isinstance(mode, int):      # a PTS_* code; one the library does not know is refused there, before any launch
+        code, P = mode, dict(POINT_MODES.values()).get(mode, 1)
+    else:
+        raise V3DError(f"coord_points_voxel: unknown mode {mode!r} (one of {sorted(POINT_MODES)})")
+    n = 14
+    shape = (V, n, n, 3) if code == PTS_SAMPLE1 else (V, n, n, P, 3)
+    pts = torch.empty(shape, dtype=x.dtype, device=x.device) if want_pts else None
+    vox = torch.empty(shape, dtype=x.dtype, device=x.device) if want_vox else None
+    ids = torch.empty(shape, dtype=torch.int32, device=x.device) if want_ids else None
+    check(lib().v3d_coord_points_voxel(_p(x), _code(x), V, S, patch, code, _f3(min_xyz), _f3(max_xyz), float(np.float32(voxel_size)),
+                                       _p(pts), _p(vox), _p(ids), _stream()), "v3d_coord_points_voxel")
+    return pts, vox, ids
+
+
 def discrete_coords(xyz, min_xyz=(-15, -15, -5), max_xyz=(15, 15, 5), voxel_size=0.1, want_ids=False):
     """K4 on arbitrary [...,3] points."""
     x = _dev(xyz, "xyz")
@@ -162,16 +191,34 @@ def reference_dim_t(num_feats, temperature=10000):
 
 
 class Sin3DTable:
-    """PE values for every integer voxel id, in the shifted layout v3d_visual_tokens reads."""
+    """PE values for every integer voxel id, in the shifted layout v3d_visual_tokens reads.  n_points > 1 (or points_layout=True):
+    PositionEmbeddingSine3D(n_points=P) in the layout v3d_visual_tokens_points reads - one [n_ids, row_elems] copy per distinct
+    shift, `shifts[c]` being copy c's."""
 
-    def __init__(self, embedding_size, n_ids, dtype, device, dim_t=None, temperature=10000, keep_f32=False):
+    def __init__(self, embedding_size, n_ids, dtype, device, dim_t=None, temperature=10000, keep_f32=False, n_points=1,
+                 points_layout=False):
         self.embedding_size = embedding_size
         self.n_ids = n_ids
         self.dtype = dtype
-        nf = embedding_size // 3
+        self.n_points = n_points
+        self.points_layout = bool(points_layout or n_points > 1)
+        nf = embedding_size // (3 * n_points)
+        self.num_feats = nf
         if dim_t is None:
             dim_t = reference_dim_t(nf, temperature)
         self.dim_t = dim_t.to(device=device, dtype=torch.float32).contiguous()
+        if self.points_layout:
+            if keep_f32:
+                raise V3DError("keep_f32 is a feature of the one-point table")
+            row, shifts = ctypes.c_int64(0), (ctypes.c_int32 * 8)()
+            copies = check(lib().v3d_sin3d_table_points_layout(embedding_size, n_points, _DT[dtype], ctypes.byref(row), shifts),
+                           "v3d_sin3d_table_points_layout")
+            self.row_elems, self.shifts = row.value, [int(shifts[c]) for c in range(copies)]
+            self.table = torch.empty((copies, n_ids, row.value), dtype=dtype, device=device)
+            self.table_f32 = None
+            check(lib().v3d_sin3d_table_build_points(_p(self.dim_t), embedding_size, n_points, n_ids, _DT[dtype], _p(self.table),
+                                                     _stream()), "v3d_sin3d_table_build_points")
+            return
         row = lib().v3d_sin3d_table_row_elems(embedding_size, _DT[dtype])
         self.row_elems = row
         self.table = torch.empty((3, n_ids, row), dtype=dtype, device=device)
@@ -180,12 +227,21 @@ class Sin3DTable:
                                           _p(self.table_f32), _stream()), "v3d_sin3d_table_build")
 
 
-def sin3d_pe(xyz, embedding_size, dim_t=None, temperature=10000):
-    """PositionEmbeddingSine3D.forward (n_points=1): xyz [B,N,3] -> [B,N,E] in xyz.dtype."""
+def sin3d_pe(xyz, embedding_size, dim_t=None, temperature=10000, n_points=1):
+    """PositionEmbeddingSine3D.forward: xyz [B,N,3] -> [B,N,E] in xyz.dtype; with n_points = P > 1, xyz [B,N,P,3] -> [B,N,E]."""
     x = _dev(xyz, "xyz")
     if dim_t is None:
-        dim_t = reference_dim_t(embedding_size // 3, temperature)
+        dim_t = reference_dim_t(embedding_size // (3 * n_points), temperature)
     dim_t = dim_t.to(device=x.device, dtype=torch.float32).contiguous()
+    if n_points > 1:
+        if x.dim() < 2 or x.shape[-1] != 3 or x.shape[-2] != n_points:
+            raise V3DError(f"xyz must be [..., {n_points}, 3], got {tuple(x.shape)}")
+        if dim_t.numel() != embedding_size // (3 * n_points):
+            raise V3DError(f"dim_t has {dim_t.numel()} entries, E={embedding_size} with {n_points} points has {embedding_size // (3 * n_points)}")
+        out = torch.empty(x.shape[:-2] + (embedding_size,), dtype=x.dtype, device=x.device)
+        check(lib().v3d_sin3d_pe_points(_p(x), _code(x), x.numel() // (3 * n_points), n_points, _p(dim_t), embedding_size, _p(out),
+                                        _stream()), "v3d_sin3d_pe_points")
+        return out
     N = x.numel() // 3
     out = torch.empty(x.shape[:-1] + (embedding_size,), dtype=x.dtype, device=x.device)
     check(lib().v3d_sin3d_pe(_p(x), _code(x), N, _p(dim_t), embedding_size, _p(out), _stream()), "v3d_sin3d_pe")
@@ -195,10 +251,14 @@ def sin3d_pe(xyz, embedding_size, dim_t=None, temperature=10000):
 # ------------------------------------------------------------------------------ fusion
 
 
-def visual_tokens(feat, ids=None, table=None, newline=None, side=27, n=14, pool=True, out=None):
+def visual_tokens(feat, ids=None, table=None, newline=None, side=27, n=14, pool=True, out=None, n_points=1, pts=None, dim_t=None):
     """K7 (+K5+K6) (+K8).  feat [V, side*side | n*n, C]; ids [V,n,n,3] int32; table Sin3DTable;
     newline [C].  Returns / fills `out` [rows, C] (rows = V*n*(n+1) with newline else V*n*n);
-    `out` may be a row-slice view of a larger [S, C] buffer (the LLM's inputs_embeds)."""
+    `out` may be a row-slice view of a larger [S, C] buffer (the LLM's inputs_embeds).
+    n_points > 1 or pts given: the P-point encodings, through visual_tokens_points; the default call launches v3d_visual_tokens."""
+    if n_points > 1 or pts is not None:
+        return visual_tokens_points(feat, ids=ids, table=table, pts=pts, dim_t=dim_t, n_points=n_points, newline=newline, side=side,
+                                    n=n, pool=pool, out=out)
     f = _dev(feat, "feat")
     V, T, C = f.shape
     flags = (VT_POOL if pool else 0) | (VT_PE if table is not None else 0) | (VT_NEWLINE if newline is not None else 0)
@@ -225,6 +285,51 @@ def visual_tokens(feat, ids=None, table=None, newline=None, side=27, n=14, pool=
         nl = _dev(newline, "newline").to(f.dtype)
     check(lib().v3d_visual_tokens(_p(f), _p(idt), _p(tbl), n_ids, _p(nl), _p(out), out.stride(0), _code(f), V, side, n, C,
                                   flags, _stream()), "v3d_visual_tokens")
+    return out
+
+
+def visual_tokens_points(feat, ids=None, table=None, pts=None, dim_t=None, n_points=1, newline=None, side=27, n=14, pool=True,
+                         out=None):
+    """v3d_visual_tokens_points: the fused kernel with P points per token.  Either ids [V,n,n,P,3] int32 + a Sin3DTable in the points
+    layout (n_points > 1 or points_layout=True), or pts [V,n,n,P,3] in feat's dtype (+ dim_t, default the reference's) for trig on the
+    fly.  Other arguments as visual_tokens."""
+    f = _dev(feat, "feat")
+    V, T, C = f.shape
+    if (pts is None) == (table is None):
+        raise V3DError("visual_tokens_points wants either pts (continuous) or ids + table (discrete)")
+    expect = side * side if pool else n * n
+    if T != expect:
+        raise V3DError(f"feat has {T} tokens per frame, expected {expect}")
+    rows = V * n * ((n + 1) if newline is not None else n)
+    if out is None:
+        out = torch.empty((rows, C), dtype=f.dtype, device=f.device)
+    if out.dtype != f.dtype or out.shape[0] != rows or out.shape[1] != C or out.stride(1) != 1:
+        raise V3DError(f"out must be [{rows},{C}] {f.dtype} with unit column stride")
+    flags = (VT_POOL if pool else 0) | VT_PE | (VT_NEWLINE if newline is not None else 0)
+    idt = tbl = pt = dt = nl = None
+    n_ids = 0
+    if pts is not None:
+        flags |= VT_CONTINUOUS
+        pt = _dev(pts, "pts")
+        if pt.dtype != f.dtype or pt.numel() != V * n * n * n_points * 3:
+            raise V3DError(f"pts must be {f.dtype} [V,n,n,{n_points},3]")
+        nf = C // (3 * n_points)
+        dt = (reference_dim_t(nf) if dim_t is None else dim_t).to(device=f.device, dtype=torch.float32).contiguous()
+        if dt.numel() != nf:
+            raise V3DError(f"dim_t has {dt.numel()} entries, C={C} with {n_points} points has {nf}")
+    else:
+        if ids is None:
+            raise V3DError("PE requested without voxel ids")
+        idt = _dev(ids, "ids")
+        if idt.dtype != torch.int32 or idt.numel() != V * n * n * n_points * 3:
+            raise V3DError(f"ids must be int32 [V,n,n,{n_points},3]")
+        if not getattr(table, "points_layout", False) or table.n_points != n_points or table.dtype != f.dtype or table.embedding_size != C:
+            raise V3DError("PE table was built for another dtype / width / number of points (Sin3DTable(..., n_points=P))")
+        tbl, n_ids = table.table, table.n_ids
+    if newline is not None:
+        nl = _dev(newline, "newline").to(f.dtype)
+    check(lib().v3d_visual_tokens_points(_p(f), _p(idt), _p(pt), _p(tbl), n_ids, _p(dt), n_points, _p(nl), _p(out), out.stride(0),
+                                         _code(f), V, side, n, C, flags, _stream()), "v3d_visual_tokens_points")
     return out
 
 

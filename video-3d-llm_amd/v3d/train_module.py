@@ -110,14 +110,25 @@ class _GroundLoss(_SampleLoss):
         return loss.detach().clone()
 
 
+def _shipped_position_type(wtype):
+    """Raises unless `wtype` parses to the shipped (avg, 1 point, discrete) encoding."""
+    from .loader import parse_position_type
+    if parse_position_type(wtype) != ("avg", 1, True):
+        raise V3DError(f"world_position_embedding_type {wtype!r}: training supports 'avg-discrete-sin3d' only; the sampled-point, min/max "
+                       "and continuous encodings are inference-only (v3d.engine.Engine)")
+
+
 class LlavaQwenTrainable(nn.Module):
     def __init__(self, tree, n_q, n_kv, head_dim=128, vit_heads=16, vit_inter=4304, rope_theta=1e6, max_pos=8192, recompute=False,
                  min_xyz=(-15, -15, -5), max_xyz=(15, 15, 5), voxel_size=0.1, ground_head_type=None, ground_temperature=0.07,
-                 ground_token_ids=None):
-        """ground_head_type: None (no grounding head modelled) or 'infonce' / 'mlp' / 'score' with tree["ground"] in the layout of
+                 ground_token_ids=None, world_position_embedding_type="avg-discrete-sin3d"):
+        """world_position_embedding_type: the checkpoint's config value; training runs the shipped 'avg-discrete-sin3d' only (the other
+        sin3d types are inference-only: DESIGN section 2) and any other type is refused here, never trained as averages.
+        ground_head_type: None (no grounding head modelled) or 'infonce' / 'mlp' / 'score' with tree["ground"] in the layout of
         train.ground_sample_forward_backward; ground_temperature: the infonce head's config.ground_head_temperature; ground_token_ids:
         config.ground_token_ids (the label ids whose row is the grounding query, llava_qwen.py:280)."""
         super().__init__()
+        _shipped_position_type(world_position_embedding_type)
         if ground_head_type is not None:
             ground_key_map(ground_head_type)                        # a known type
             if "ground" not in tree:
