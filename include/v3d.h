@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define V3D_ABI_VERSION 7   /* 2: *_rows decode entries, fp8 path, a7 / a3 device entries; 3: rope_kv_store, add_row, ...; 4: resize_bicubic, eos_update, embed_grad bounds; 6: sumsq, *_rows entries take 1..32 rows; 7: attention_shared_prefix; ground_scores_rows, add_rows and the v3d_beam_* entries were ADDED under 7 (no entry changed); so were the v3d_sample_* entries, and v3d_coord_points_voxel, v3d_sin3d_table_points_layout, v3d_sin3d_table_build_points, v3d_sin3d_pe_points and v3d_visual_tokens_points */
+#define V3D_ABI_VERSION 7   /* 2: *_rows decode entries, fp8 path, a7 / a3 device entries; 3: rope_kv_store, add_row, ...; 4: resize_bicubic, eos_update, embed_grad bounds; 6: sumsq, *_rows entries take 1..32 rows; 7: attention_shared_prefix; ground_scores_rows, add_rows and the v3d_beam_* entries were ADDED under 7 (no entry changed); so were the v3d_sample_* entries, and v3d_coord_points_voxel, v3d_sin3d_table_points_layout, v3d_sin3d_table_build_points, v3d_sin3d_pe_points and v3d_visual_tokens_points; and v3d_pe_mlp_hidden, v3d_visual_tokens_rows, v3d_visual_tokens_rows_grad, v3d_pe_mlp_wgrad_workspace_bytes and v3d_pe_mlp_wgrad */
 
 enum { V3D_F32 = 0, V3D_F16 = 1, V3D_BF16 = 2 };
 enum { V3D_U8_HWC = 16 };   /* v3d_resize_bicubic_u8 only: 8-bit interleaved output, no normalisation */
@@ -184,6 +184,39 @@ enum { V3D_VT_CONTINUOUS = 8 };
 int v3d_visual_tokens_points(const void* feat, const int32_t* ids, const void* pts, const void* table, int n_ids,
                              const float* dim_t, int n_points, const void* newline, void* out, int64_t out_stride,
                              int dtype, int V, int side, int n, int C, int flags, void* stream);
+
+/* Added under ABI 7 (no entry changed).  PositionEmbeddingMLP (position_encoding.py:52-84; selected by an `mlp`
+ * world_position_embedding_type, llava_arch.py:60-61): Linear(3, 512) -> LayerNorm(512, eps) -> ReLU -> Linear(512, E).
+ * The rule is DESIGN section 2, "The MLP position encoding, stated once".  16-bit dtypes only.
+ *
+ * The first three stages: x [N,3], w0 [hidden,3], b0 / ln_w / ln_b [hidden], all dtype ->
+ *     z = T(x . w0^T + b0)                        (three fused multiply-adds per element, one rounding)
+ *     h = relu(T((z - mean) * rstd * ln_w + ln_b))  (row statistics of the ROUNDED z in f32)
+ * h [N,hidden] dtype; z [N,hidden] dtype is optional (NULL: not stored) - training keeps it, the tests isolate the stages
+ * with it.  hidden must be 512 (the reference's only width; one wave per row, 8 elements per lane); any N >= 1; rows are
+ * independent (a NaN coordinate gives a NaN row and nothing else).  The last stage is v3d_gemm(h, w3, V3D_EPI_BIAS). */
+int v3d_pe_mlp_hidden(const void* x, const void* w0, const void* b0, const void* ln_w, const void* ln_b, float eps,
+                      int64_t N, int hidden, int dtype, void* z, void* h, void* stream);
+
+/* v3d_visual_tokens with the PE read from rows: pe [V*n*n, C] dtype, row stride pe_stride (a multiple of 8), row
+ * (v*n + oh)*n + ow added to output token (v, oh, ow).  Flags POOL and NEWLINE as there (PE is implied); the same rounding
+ * points: token = T(T(pooled) + pe).  feat is read once and out written once; the PE rows are the extra traffic. */
+int v3d_visual_tokens_rows(const void* feat, const void* pe, int64_t pe_stride, const void* newline, void* out,
+                           int64_t out_stride, int dtype, int V, int side, int n, int C, int flags, void* stream);
+
+/* Backward of v3d_visual_tokens_rows: dfeat and dnewline exactly as v3d_visual_tokens_grad gives them (same kernels), plus
+ * dpe [V*n*n, C] dtype (row stride dpe_stride): the gradient rows of the tokens without the newline rows - the add passes
+ * the gradient through, and the two linears below it take it as a plain matrix. */
+int v3d_visual_tokens_rows_grad(const void* dout, int64_t dout_stride, void* dfeat, float* dnewline, void* dpe,
+                                int64_t dpe_stride, int dtype, int V, int side, int n, int C, int flags, void* stream);
+
+/* Weight gradient of the first Linear: dw0[j, a] = sum over rows r of dz[r, j] * x[r, a]; dz [rows, hidden] dtype (row
+ * stride lddz), x [rows, 3] dtype, dw0 [hidden, 3] in out_dtype.  f32, fixed order, no atomics (32-row partials in row order,
+ * then the partials as v3d_colsum sums them): run-to-run identical.  hidden must be 512.
+ * workspace: v3d_pe_mlp_wgrad_workspace_bytes(rows, hidden) bytes. */
+int64_t v3d_pe_mlp_wgrad_workspace_bytes(int64_t rows, int hidden);
+int v3d_pe_mlp_wgrad(const void* dz, int64_t lddz, const void* x, int64_t rows, int hidden, int dtype, float* workspace,
+                     void* dw0, int out_dtype, void* stream);
 
 /* K9  embed_tokens gather for the text segments (llava_arch.py:693): out[i,:] = table[ids[i],:]. */
 int v3d_embed_gather(const void* table, int64_t vocab, int C, const int64_t* ids, int64_t n,

@@ -3,9 +3,9 @@
 `LlavaMetaModel` / `LlavaMetaForCausalLM` keep the reference's names, method signatures and return conventions for the
 video + sin3d position encoding + bilinear-pool + `grid`-newline branch - `avg-discrete-sin3d` is the one every 3-D eval
 driver and the shipped training script select (scripts/3d/train/train_multi.sh:78-87); the paper's other sin3d types
-(avg / sample9 / sample5 / sample1 / minmax, with or without `discrete`) run for inference - and launch kernels of
-libv3d_hip.so through v3d.engine.Engine.  Branches those scripts never reach (anyres / unpad image grids, faster-video,
-mrope, llava3d, mlp PE, multi-image prompts, batch > 1) raise NotImplementedError instead of computing something else.
+(avg / sample9 / sample5 / sample1 / minmax, with or without `discrete`) and the `mlp` types (avg / sample1) run for inference -
+and launch kernels of libv3d_hip.so through v3d.engine.Engine.  Branches those scripts never reach (anyres / unpad image grids,
+faster-video, mrope, llava3d, multi-image prompts, batch > 1) raise NotImplementedError instead of computing something else.
 """
 import math
 
@@ -37,14 +37,20 @@ class LlavaMetaModel:
     vision tower, projector, image_newline, embed_tokens, world_position_embedding - all views of one Engine."""
 
     def __init__(self, config, engine, vision_tower):
-        from .position_encoding import PositionEmbeddingSine3D
+        from .position_encoding import PositionEmbeddingMLP, PositionEmbeddingSine3D
         self.config = config
         self._engine = engine
         self.vision_tower = vision_tower
         self.mm_projector = _Projector(engine)
         self.image_newline = engine.newline
         # llava_arch.py:51-63: the module is built for the type's number of points
-        self.world_position_embedding = PositionEmbeddingSine3D(config.hidden_size, n_points=engine.cfg.n_points)
+        if engine.pe_kind == "mlp":        # llava_arch.py:60-61: `mlp` wins; the module's parameters are the engine's six tensors
+            self.world_position_embedding = PositionEmbeddingMLP(config.hidden_size, n_points=engine.cfg.n_points)
+            for name, t in zip(engine.pe_mlp, self.world_position_embedding.mlp.parameters()):      # w0, b0, ln_w, ln_b, w3, b3: the module's order
+                t.data = engine.pe_mlp[name]
+                t.requires_grad_(False)
+        else:
+            self.world_position_embedding = PositionEmbeddingSine3D(config.hidden_size, n_points=engine.cfg.n_points)
 
     def get_vision_tower(self):
         return self.vision_tower
@@ -117,8 +123,11 @@ class LlavaMetaForCausalLM:
         (unused, may be None, for a type without `discrete`)."""
         from v3d.loader import parse_position_type
         c = self.config
-        aggregation, n_points, discrete = parse_position_type(getattr(c, "world_position_embedding_type", "avg-discrete-sin3d"))
         side = self.get_vision_tower().num_patches_per_side
+        if self.engine.pe_kind == "mlp":        # the module's input from the engine, its PE rows, one fused pass
+            pe = ops.pe_mlp(self.engine.voxel_ids(world_coords), self.engine.pe_mlp)
+            return ops.visual_tokens_rows(image_feature, pe, self.get_model().image_newline, side=side, n=math.ceil(side / 2), pool=True, out=out)
+        aggregation, n_points, discrete = parse_position_type(getattr(c, "world_position_embedding_type", "avg-discrete-sin3d"))
         if aggregation == "avg":
             pts, _, ids = ops.coord_pool_voxel(world_coords, 27, c.min_xyz_range, c.max_xyz_range, c.voxel_size,
                                                want_avg=not discrete, want_vox=False, want_ids=discrete)
@@ -148,7 +157,7 @@ class LlavaMetaForCausalLM:
             raise NotImplementedError("the accelerated path takes one video sample per call (batch 1, modalities=['video']), "
                                       "as every 3-D eval driver passes")
         if video_dict is None or "world_coords" not in video_dict:
-            raise ValueError("video_dict['world_coords'] is required (every sin3d world_position_embedding_type takes its PE from them)")
+            raise ValueError("video_dict['world_coords'] is required (every world_position_embedding_type takes its PE from them)")
         if past_key_values is not None:
             raise NotImplementedError("an external past_key_values cache is not supported: the engine owns the KV cache")
         if attention_mask is not None and not bool(attention_mask.bool().all()):

@@ -56,6 +56,11 @@ SIGNATURES = {
     "v3d_sin3d_table_build_points": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p]),
     "v3d_sin3d_pe_points": (c_i, [c_p, c_i, c_l, c_i, c_p, c_i, c_p, c_p]),
     "v3d_visual_tokens_points": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "v3d_pe_mlp_hidden": (c_i, [c_p, c_p, c_p, c_p, c_p, c_f, c_l, c_i, c_i, c_p, c_p, c_p]),
+    "v3d_visual_tokens_rows": (c_i, [c_p, c_p, c_l, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "v3d_visual_tokens_rows_grad": (c_i, [c_p, c_l, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "v3d_pe_mlp_wgrad_workspace_bytes": (c_l, [c_l, c_i]),
+    "v3d_pe_mlp_wgrad": (c_i, [c_p, c_l, c_p, c_l, c_i, c_i, c_p, c_p, c_i, c_p]),
     "v3d_gemm": (c_i, [c_p, c_l, c_p, c_l, c_p, c_p, c_l, c_i, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_p]),
     "v3d_gemm_layout": (c_i, [c_p, c_l, c_i, c_p, c_l, c_i, c_p, c_p, c_l, c_i, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_p]),
     "v3d_quantize_fp8_rows": (c_i, [c_p, c_l, c_l, c_i, c_i, c_p, c_l, c_p, c_p]),

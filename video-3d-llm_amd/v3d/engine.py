@@ -64,6 +64,14 @@ class EngineConfig:
     aggregation: str = "avg"               # 'avg' | 'sample9' | 'sample5' | 'sample1' | 'minmax'
     n_points: int = 1                      # 1 | 9 | 5 | 1 | 2
     discrete: bool = True
+    # which module encodes them (loader.parse_position_encoder): 'sin3d' (PositionEmbeddingSine3D, no parameters) or 'mlp'
+    # (PositionEmbeddingMLP: six tensors of the checkpoint; avg / sample1 only)
+    pe_kind: str = "sin3d"
+
+
+# PositionEmbeddingMLP's tensors (position_encoding.py:64-69): the engine's / the training tree's leaf name -> the key behind the prefix
+PE_MLP_PREFIX = "model.world_position_embedding.mlp."
+PE_MLP_KEYS = {"w0": "0.weight", "b0": "0.bias", "ln_w": "1.weight", "ln_b": "1.bias", "w3": "3.weight", "b3": "3.bias"}
 
 
 def random_state_dict(cfg: EngineConfig, dtype, device, seed=0, std=0.02, ground_head=False):
@@ -192,9 +200,23 @@ class Engine:
                                cfg.max_xyz[2] - cfg.min_xyz[2])) / cfg.voxel_size)) + 1
         if {"avg": 1, **{k: p for k, (_, p) in ops.POINT_MODES.items()}}.get(cfg.aggregation) != cfg.n_points:
             raise V3DError(f"aggregation {cfg.aggregation!r} with n_points {cfg.n_points}: see loader.parse_position_type")
+        if cfg.pe_kind not in ("sin3d", "mlp"):
+            raise V3DError(f"pe_kind {cfg.pe_kind!r}: 'sin3d' or 'mlp' (loader.parse_position_encoder)")
+        self.pe_mlp = None
+        if cfg.pe_kind == "mlp":         # PositionEmbeddingMLP: the six tensors, no table and no dim_t
+            if cfg.n_points != 1:
+                raise V3DError(f"pe_kind 'mlp' with aggregation {cfg.aggregation!r}: one point per patch (avg, sample1) only")
+            for k in PE_MLP_KEYS.values():
+                if PE_MLP_PREFIX + k not in sd:
+                    raise V3DError(f"pe_kind 'mlp' but the state dict has no {PE_MLP_PREFIX + k}")
+            self.pe_mlp = {name: sd[PE_MLP_PREFIX + k].contiguous() for name, k in PE_MLP_KEYS.items()}
+            if tuple(self.pe_mlp["w0"].shape) != (ops.PE_MLP_HIDDEN, 3) or tuple(self.pe_mlp["w3"].shape) != (l.hidden, ops.PE_MLP_HIDDEN):
+                raise V3DError(f"PositionEmbeddingMLP weights {tuple(self.pe_mlp['w0'].shape)} / {tuple(self.pe_mlp['w3'].shape)}: "
+                               f"[{ops.PE_MLP_HIDDEN},3] and [{l.hidden},{ops.PE_MLP_HIDDEN}] expected")
+        sin3d = cfg.pe_kind == "sin3d"
         # PE values per voxel id for the configured number of points; a type without `discrete` evaluates the trig per token instead
-        self.pe_table = ops.Sin3DTable(l.hidden, n_ids, dtype, device, n_points=cfg.n_points) if cfg.discrete else None
-        self._pe_dim_t = None if cfg.discrete else ops.reference_dim_t(l.hidden // (3 * cfg.n_points)).to(device)
+        self.pe_table = ops.Sin3DTable(l.hidden, n_ids, dtype, device, n_points=cfg.n_points) if sin3d and cfg.discrete else None
+        self._pe_dim_t = ops.reference_dim_t(l.hidden // (3 * cfg.n_points)).to(device) if sin3d and not cfg.discrete else None
         self.rope = ops.RopeTable(self.hd, l.max_pos, l.rope_theta, dtype, device)
         self._alloc(max_frames)
 
@@ -306,6 +328,10 @@ class Engine:
         w.p_h, w.feat = z(T, l.hidden), z(T, l.hidden)
         w.l_h = z(S, l.hidden)
         w.l_qkv, w.l_att, w.l_act = z(S, self.l_nqkv), z(S, l.hidden), z(S, l.inter)
+        w.pe_h = w.pe_rows = None
+        if self.cfg.pe_kind == "mlp":                  # the MLP position encoding's hidden rows and PE rows of the visual tokens
+            n_tok = self.max_frames * self.cfg.pool_out ** 2
+            w.pe_h, w.pe_rows = z(n_tok, ops.PE_MLP_HIDDEN), z(n_tok, l.hidden)
         w.l_q8 = w.l_s8 = None
         if self.llm_quant:                             # e4m3 image + row scales of the current GEMM's activations
             w.l_q8 = torch.zeros((S, max(l.hidden, l.inter)), dtype=torch.uint8, device=dev)
@@ -405,14 +431,28 @@ class Engine:
 
     # ------------------------------------------------------------------ fusion (a11-a17)
     @property
+    def pe_kind(self):
+        """'sin3d' | 'mlp': the module that encodes the coordinates (EngineConfig.pe_kind)."""
+        return self.cfg.pe_kind
+
+    @property
     def pe_dim_t(self):
         return self.pe_table.dim_t if self.pe_table is not None else self._pe_dim_t
 
     def voxel_ids(self, world_coords):
         """[F,384,384,3] (model dtype) -> int32 [F,14,14,3]   (llava_arch.py:403, 416).  For the other types (llava_arch.py:395-420):
         [F,14,14,P,3] with P points per patch ([F,14,14,3] for sample1), int32 voxel ids when the type is `discrete`, else the
-        aggregated coordinates themselves in the model dtype - whichever build_inputs_embeds takes the PE of."""
+        aggregated coordinates themselves in the model dtype - whichever build_inputs_embeds takes the PE of.  pe_kind 'mlp': always a
+        model-dtype tensor [F,14,14,3], the integer-VALUED voxel coordinates with `discrete` (what the reference feeds the module)."""
         c = self.cfg
+        if self.pe_kind == "mlp":       # the module's input: the dtype-VALUED coordinates (`vox` with `discrete`, never the int32 ids)
+            if c.aggregation == "avg":
+                avg, vox, _ = ops.coord_pool_voxel(world_coords, 27, c.min_xyz, c.max_xyz, c.voxel_size, want_avg=not c.discrete,
+                                                   want_vox=c.discrete, want_ids=False)
+            else:
+                avg, vox, _ = ops.coord_points_voxel(world_coords, c.aggregation, 27, c.min_xyz, c.max_xyz, c.voxel_size,
+                                                     want_pts=not c.discrete, want_vox=c.discrete, want_ids=False)
+            return vox if c.discrete else avg
         if c.aggregation == "avg" and c.discrete:
             _, _, ids = ops.coord_pool_voxel(world_coords, 27, c.min_xyz, c.max_xyz, c.voxel_size, want_avg=False, want_vox=False)
             return ids
@@ -428,6 +468,8 @@ class Engine:
         c = self.cfg
         if c.discrete:
             centres = ops.discrete_coords(centres, c.min_xyz, c.max_xyz, c.voxel_size)
+        if self.pe_kind == "mlp":
+            return ops.pe_mlp(centres, self.pe_mlp)
         if c.n_points > 1:
             centres = centres[:, None, :].expand(-1, c.n_points, -1).contiguous()
         return ops.sin3d_pe(centres[None], c.llm.hidden, dim_t=self.pe_dim_t, n_points=c.n_points)[0]
@@ -454,7 +496,10 @@ class Engine:
         up = lambda t: (t if t.is_cuda else t.pin_memory().to(self.device, non_blocking=True))      # noqa: E731  (no host-blocking pageable copy)
         if len(pre):
             ops.embed_gather(self.embed, up(pre), out=x[: len(pre)])
-        if self.cfg.discrete:
+        if self.pe_kind == "mlp":       # `ids` holds the module's input (voxel_ids): PE rows from the MLP, added by the fused kernel
+            vt = lambda: ops.visual_tokens_rows(feats, ops.pe_mlp(ids, self.pe_mlp, out=self.ws.pe_rows, h_out=self.ws.pe_h), self.newline,      # noqa: E731
+                                                side=side, n=n, pool=True, out=x[len(pre): len(pre) + n_vis])
+        elif self.cfg.discrete:
             vt = lambda: ops.visual_tokens(feats, ids, self.pe_table, self.newline, side=side, n=n, pool=True, out=x[len(pre): len(pre) + n_vis],      # noqa: E731
                                            n_points=self.cfg.n_points)
         else:       # `ids` holds the aggregated coordinates (voxel_ids): trig per token

@@ -11,7 +11,7 @@ import os
 import torch
 
 from ._native import V3DError
-from .engine import EngineConfig, LlmConfig, VitConfig
+from .engine import PE_MLP_KEYS, PE_MLP_PREFIX, EngineConfig, LlmConfig, VitConfig
 
 VIT_PREFIX = "model.vision_tower.vision_tower.vision_model."
 
@@ -58,18 +58,53 @@ def read_tower_weights(tower_dir):
     return out
 
 
+_AGGREGATIONS = (("avg", 1), ("sample9", 9), ("sample5", 5), ("sample1", 1), ("minmax", 2))
+
+
+def _parse_aggregation(wtype):
+    """The first of avg / sample9 / sample5 / sample1 / minmax the string contains (llava_arch.py:395-407) and `discrete`."""
+    for aggregation, n_points in _AGGREGATIONS:
+        if aggregation in wtype:
+            return aggregation, n_points, "discrete" in wtype
+    raise V3DError(f"world_position_embedding_type {wtype!r} names none of avg / sample9 / sample5 / sample1 / minmax")
+
+
 def parse_position_type(wtype):
     """world_position_embedding_type -> (aggregation, n_points, discrete), with the reference's precedence (llava_arch.py:395-407,
-    :51-58): the first of avg / sample9 / sample5 / sample1 / minmax the string contains; `discrete` = voxelise before the PE; `sin3d`
-    is the only PE on the accelerated path (`mlp` needs checkpoint weights, `mrope` another rotary rule: DESIGN section 2)."""
+    :51-58): the first of avg / sample9 / sample5 / sample1 / minmax the string contains; `discrete` = voxelise before the PE.  This is
+    the sin3d parser: an `mlp` type (parse_position_encoder, parse_mlp_position_type) needs checkpoint weights, `mrope` another rotary rule
+    (DESIGN section 2)."""
     if "mrope" in wtype or "mlp" in wtype:
         raise V3DError(f"world_position_embedding_type {wtype!r}: the 'mlp' and 'mrope' encodings are not on the accelerated path")
     if "sin3d" not in wtype:
         raise V3DError(f"world_position_embedding_type {wtype!r}: only 'sin3d' encodings are on the accelerated path")
-    for aggregation, n_points in (("avg", 1), ("sample9", 9), ("sample5", 5), ("sample1", 1), ("minmax", 2)):
-        if aggregation in wtype:
-            return aggregation, n_points, "discrete" in wtype
-    raise V3DError(f"world_position_embedding_type {wtype!r} names none of avg / sample9 / sample5 / sample1 / minmax")
+    return _parse_aggregation(wtype)
+
+
+def parse_position_encoder(wtype):
+    """world_position_embedding_type -> 'sin3d' | 'mlp': which module encodes the coordinates.  `mlp` in the string selects
+    PositionEmbeddingMLP and wins over `sin3d` (llava_arch.py:60-63); it is accepted with the one-point aggregations only (avg, sample1,
+    each with or without `discrete`): with sample9 / sample5 / minmax the reference's module names an undefined `num_feats`
+    (position_encoding.py:79) and cannot run.  `mrope` is refused: the reference tests its flag before it sets it (llava_arch.py:415-423)
+    and defines no decode positions."""
+    if "mrope" in wtype:
+        raise V3DError(f"world_position_embedding_type {wtype!r}: 'mrope' does not run in the reference (its flag is tested before it is set, "
+                       "llava_arch.py:415-423, and decode positions are undefined); it is not on the accelerated path")
+    if "mlp" in wtype:
+        aggregation, n_points, _ = _parse_aggregation(wtype)
+        if n_points != 1:
+            raise V3DError(f"world_position_embedding_type {wtype!r}: the 'mlp' encoding takes one point per patch (avg, sample1); with "
+                           f"{aggregation!r} the reference module names an undefined `num_feats` (position_encoding.py:79) and cannot run")
+        return "mlp"
+    parse_position_type(wtype)
+    return "sin3d"
+
+
+def parse_mlp_position_type(wtype):
+    """(aggregation, n_points, discrete) of an `mlp` type; raises for every other string."""
+    if parse_position_encoder(wtype) != "mlp":
+        raise V3DError(f"world_position_embedding_type {wtype!r} is not an 'mlp' type")
+    return _parse_aggregation(wtype)
 
 
 def engine_config(hf_config, sd, max_positions=None):
@@ -78,7 +113,15 @@ def engine_config(hf_config, sd, max_positions=None):
     (siglip_encoder.py:570): a checkpoint saved AFTER that deletion (the tower was trained / saved with the model) has it
     gone already, a raw SigLIP directory still has all 27."""
     c = hf_config
-    aggregation, n_points, discrete = parse_position_type(getattr(c, "world_position_embedding_type", "avg-discrete-sin3d"))
+    wtype = getattr(c, "world_position_embedding_type", "avg-discrete-sin3d")
+    pe_kind = "mlp" if "mlp" in wtype and "mrope" not in wtype else "sin3d"
+    if pe_kind == "mlp":       # accepted only with the module's six tensors; a state dict that has them under a sin3d type ignores them
+        missing = [PE_MLP_PREFIX + k for k in PE_MLP_KEYS.values() if PE_MLP_PREFIX + k not in sd]
+        if missing:
+            raise V3DError(f"world_position_embedding_type {wtype!r} needs the PositionEmbeddingMLP weights, the state dict has no {missing[0]}")
+        aggregation, n_points, discrete = parse_mlp_position_type(wtype)
+    else:
+        aggregation, n_points, discrete = parse_position_type(wtype)
     for key, want in (("mm_spatial_pool_mode", "bilinear"), ("mm_newline_position", "grid"), ("mm_projector_type", "mlp2x_gelu")):
         got = getattr(c, key, want)
         if got != want:
@@ -103,7 +146,7 @@ def engine_config(hf_config, sd, max_positions=None):
                         max_xyz=tuple(getattr(c, "max_xyz_range", (15, 15, 5))), voxel_size=float(getattr(c, "voxel_size", 0.1)),
                         ground_head_type=getattr(c, "ground_head_type", None) or "infonce",
                         object_feature_type=getattr(c, "object_feature_type", None) or "patch14-pe",
-                        aggregation=aggregation, n_points=n_points, discrete=discrete)
+                        aggregation=aggregation, n_points=n_points, discrete=discrete, pe_kind=pe_kind)
 
 
 def drop_deleted_tower_layer(sd, tower_from_raw_siglip):

@@ -333,6 +333,71 @@ def visual_tokens_points(feat, ids=None, table=None, pts=None, dim_t=None, n_poi
     return out
 
 
+PE_MLP_HIDDEN = 512          # PositionEmbeddingMLP.hidden_size (position_encoding.py:63)
+
+
+def pe_mlp_hidden(x, w0, b0, ln_w, ln_b, eps=1e-5, want_z=False, out=None):
+    """The first three stages of PositionEmbeddingMLP: x [..., 3] -> h = relu(LayerNorm(x @ w0.T + b0)) [N, 512] with the 16-bit modules'
+    rounding points (v3d_pe_mlp_hidden).  want_z: returns (z, h), z the rounded output of the first Linear.  out: a contiguous buffer of
+    at least N rows that takes h (its first N rows are returned)."""
+    x = _dev(x, "x")
+    if x.shape[-1] != 3:
+        raise V3DError("x must end in a dimension of 3")
+    N = x.numel() // 3
+    Hh = w0.shape[0]
+    ws = [_dev(t, nme) for t, nme in ((w0, "w0"), (b0, "b0"), (ln_w, "ln_w"), (ln_b, "ln_b"))]
+    if tuple(ws[0].shape) != (Hh, 3) or any(t.numel() != Hh for t in ws[1:]) or any(t.dtype != x.dtype for t in ws):
+        raise V3DError(f"pe_mlp_hidden: w0 [{Hh},3], b0 / ln_w / ln_b [{Hh}] in {x.dtype} expected")
+    if out is None:
+        h = torch.empty((N, Hh), dtype=x.dtype, device=x.device)
+    else:
+        _rows_fit(out, N, Hh, x.dtype, "pe_mlp_hidden")
+        if not out.is_contiguous() or out.dim() != 2 or out.shape[1] != Hh:
+            raise V3DError(f"pe_mlp_hidden: out must be a contiguous [rows, {Hh}] buffer")
+        h = out[:N]
+    z = torch.empty((N, Hh), dtype=x.dtype, device=x.device) if want_z else None
+    if N:
+        check(lib().v3d_pe_mlp_hidden(_p(x), _p(ws[0]), _p(ws[1]), _p(ws[2]), _p(ws[3]), float(eps), N, Hh, _code(x), _p(z), _p(h), _stream()),
+              "v3d_pe_mlp_hidden")
+    return (z, h) if want_z else h
+
+
+def pe_mlp(x, p, want_saved=False, out=None, h_out=None):
+    """PositionEmbeddingMLP.forward on x [..., 3] -> PE rows [N, E]: v3d_pe_mlp_hidden, then the second Linear on v3d_gemm (EPI_BIAS).
+    p holds {w0, b0, ln_w, ln_b, w3, b3}.  want_saved: returns (pe, (x, z, h)) for pe_mlp_backward.  out [>= N, E] / h_out [>= N, 512]:
+    buffers of the caller's for the PE rows and the hidden rows (the engine's prefill allocates nothing)."""
+    x = _dev(x, "x").reshape(-1, 3)
+    if x.shape[0] == 0:
+        pe = torch.empty((0, p["w3"].shape[0]), dtype=x.dtype, device=x.device)
+        return (pe, (x, None, None)) if want_saved else pe
+    r = pe_mlp_hidden(x, p["w0"], p["b0"], p["ln_w"], p["ln_b"], 1e-5, want_z=want_saved, out=h_out)
+    z, h = r if want_saved else (None, r)
+    pe = gemm(h, p["w3"], bias=p["b3"], epilogue=EPI_BIAS, out=None if out is None else out[: x.shape[0]])
+    return (pe, (x, z, h)) if want_saved else pe
+
+
+def visual_tokens_rows(feat, pe, newline=None, side=27, n=14, pool=True, out=None):
+    """v3d_visual_tokens_rows: visual_tokens with the PE taken from rows pe [V*n*n, C] (row stride >= C) instead of ids + a table."""
+    f = _dev(feat, "feat")
+    V, T, C = f.shape
+    expect = side * side if pool else n * n
+    if T != expect:
+        raise V3DError(f"feat has {T} tokens per frame, expected {expect}")
+    if not isinstance(pe, torch.Tensor) or not pe.is_cuda or pe.dtype != f.dtype or pe.dim() != 2 or pe.shape[0] != V * n * n or pe.shape[1] != C \
+            or pe.stride(1) != 1:
+        raise V3DError(f"pe must be a [{V * n * n},{C}] {f.dtype} device tensor with unit column stride")
+    rows = V * n * ((n + 1) if newline is not None else n)
+    if out is None:
+        out = torch.empty((rows, C), dtype=f.dtype, device=f.device)
+    if out.dtype != f.dtype or out.shape[0] != rows or out.shape[1] != C or out.stride(1) != 1:
+        raise V3DError(f"out must be [{rows},{C}] {f.dtype} with unit column stride")
+    nl = _dev(newline, "newline").to(f.dtype) if newline is not None else None
+    flags = (VT_POOL if pool else 0) | VT_PE | (VT_NEWLINE if newline is not None else 0)
+    check(lib().v3d_visual_tokens_rows(_p(f), _p(pe), pe.stride(0), _p(nl), _p(out), out.stride(0), _code(f), V, side, n, C, flags, _stream()),
+          "v3d_visual_tokens_rows")
+    return out
+
+
 def embed_gather(weight, ids, out=None):
     w = _dev(weight, "weight")
     i = _dev(ids, "ids").to(torch.int64).reshape(-1)
@@ -1270,6 +1335,35 @@ def visual_tokens_grad(dout, V, side=27, n=14, newline=True):
     flags = VT_POOL | VT_PE | (VT_NEWLINE if newline else 0)
     check(lib().v3d_visual_tokens_grad(_p(g), g.stride(0), _p(dfeat), _p(dnl), _code(g), V, side, n, C, flags, _stream()), "v3d_visual_tokens_grad")
     return dfeat, dnl
+
+
+def visual_tokens_rows_grad(dout, V, side=27, n=14, newline=True):
+    """Backward of visual_tokens_rows(pool=True, pe [, newline]): returns (dfeat, dnewline) as visual_tokens_grad does and dpe [V*n*n, C],
+    the gradient rows of the tokens without the newline rows."""
+    g = _dev(dout, "dout")
+    rows, C = g.shape
+    if rows != V * n * ((n + 1) if newline else n):
+        raise V3DError(f"visual_tokens_rows_grad: dout has {rows} rows, expected {V * n * ((n + 1) if newline else n)}")
+    dfeat = torch.empty((V, side * side, C), dtype=g.dtype, device=g.device)
+    dnl = torch.empty(C, dtype=torch.float32, device=g.device) if newline else None
+    dpe = torch.empty((V * n * n, C), dtype=g.dtype, device=g.device)
+    flags = VT_POOL | VT_PE | (VT_NEWLINE if newline else 0)
+    check(lib().v3d_visual_tokens_rows_grad(_p(g), g.stride(0), _p(dfeat), _p(dnl), _p(dpe), dpe.stride(0), _code(g), V, side, n, C, flags,
+                                            _stream()), "v3d_visual_tokens_rows_grad")
+    return dfeat, dnl, dpe
+
+
+def pe_mlp_wgrad(dz, x, dtype=None):
+    """dw0 [512, 3] = dz^T . x for dz [rows, 512] and x [rows, 3] (16-bit): f32 sums in a fixed order (v3d_pe_mlp_wgrad), in `dtype`
+    (default dz's)."""
+    dz, x = _dev(dz, "dz"), _dev(x, "x")
+    rows, Hh = dz.shape
+    if tuple(x.shape) != (rows, 3) or x.dtype != dz.dtype:
+        raise V3DError(f"pe_mlp_wgrad: x must be [{rows},3] {dz.dtype}")
+    ws = torch.empty(max(1, lib().v3d_pe_mlp_wgrad_workspace_bytes(rows, Hh) // 4), dtype=torch.float32, device=dz.device)
+    out = torch.empty((Hh, 3), dtype=dtype or dz.dtype, device=dz.device)
+    check(lib().v3d_pe_mlp_wgrad(_p(dz), dz.stride(0), _p(x), rows, Hh, _code(dz), _p(ws), _p(out), _DT[out.dtype], _stream()), "v3d_pe_mlp_wgrad")
+    return out
 
 
 # ------------------------------------------------------------------------------ backward of the dense blocks (configs[4])

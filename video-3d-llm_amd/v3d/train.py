@@ -484,12 +484,17 @@ def projector_backward(dy, saved, w1, w2, need_dx=True):
     return dx, {"w1": dw1, "b1": db1, "w2": dw2, "b2": db2}
 
 
-def inputs_embeds_backward(dx, n_pre, frames, text_rows, text_ids, embed_grad_out, side=27, n=14):
+def inputs_embeds_backward(dx, n_pre, frames, text_rows, text_ids, embed_grad_out, side=27, n=14, want_dpe=False):
     """Backward of the splice (llava_arch.py:650-836, one sample, one <image>): dx [S, H] = gradient of inputs_embeds
     [n_pre text rows | frames * n * (n + 1) visual rows | text rows].  The visual rows go back through newline / PE add / bilinear pool
     (v3d_visual_tokens_grad) to the projector's output [frames, side * side, H] and to image_newline; the text rows are summed per
-    token id into embed_tokens' gradient (embed_grad_out [vocab, H], pre-zeroed).  Returns (dfeat, dnewline)."""
+    token id into embed_tokens' gradient (embed_grad_out [vocab, H], pre-zeroed).  Returns (dfeat, dnewline); want_dpe (the PE rows came
+    from PositionEmbeddingMLP): (dfeat, dnewline, dpe [frames * n * n, H]) through v3d_visual_tokens_rows_grad."""
     n_vis = frames * n * (n + 1)
+    if want_dpe:
+        dfeat, dnl, dpe = ops.visual_tokens_rows_grad(dx[n_pre:n_pre + n_vis], frames, side=side, n=n, newline=True)
+        ops.embed_grad(dx, text_rows, text_ids, embed_grad_out)
+        return dfeat, dnl, dpe
     dfeat, dnl = ops.visual_tokens_grad(dx[n_pre:n_pre + n_vis], frames, side=side, n=n, newline=True)
     ops.embed_grad(dx, text_rows, text_ids, embed_grad_out)
     return dfeat, dnl
@@ -595,16 +600,22 @@ def siglip_tower_backward(dh, saved, vp, frames, tokens=729):
     return {"patch_w": d_patch_w, "patch_b": d_patch_b, "pos": d_pos, "layers": grads}
 
 
-def _build_inputs_embeds(params, y, voxel_ids, pe_table, pre_ids, post_ids, frames, tokens, side, n, coord_rows=None, coord_pe=None):
+def _build_inputs_embeds(params, y, voxel_ids, pe_table, pre_ids, post_ids, frames, tokens, side, n, coord_rows=None, coord_pe=None, pe_mlp=None,
+                         pe_rows=None):
     """prepare_inputs_labels_for_multimodal for one sample with one <image> (llava_arch.py:650-836): text rows | visual rows | text rows;
     coord_rows / coord_pe: the PE of the discretised box centre added to the rows of the <coord> text tokens (Scan2Cap prompts,
-    llava_arch.py:416-417, 697-700) - no parameters, so the backward passes those rows' gradient through to the embedding."""
+    llava_arch.py:416-417, 697-700) - under sin3d no parameters, so the backward passes those rows' gradient through to the embedding.
+    pe_mlp (the PositionEmbeddingMLP group {w0, b0, ln_w, ln_b, w3, b3}): the visual rows take pe_rows [frames * n * n, H], the module's
+    output for the token coordinates (_pe_mlp_forward), through v3d_visual_tokens_rows; voxel_ids and pe_table are not read."""
     H = y.shape[1]
     n_pre, n_post, n_vis = pre_ids.numel(), post_ids.numel(), frames * n * (n + 1)
     x = torch.empty((n_pre + n_vis + n_post, H), dtype=y.dtype, device=y.device)
     if n_pre:
         ops.embed_gather(params["embed"], pre_ids, out=x[:n_pre])
-    ops.visual_tokens(y.view(frames, tokens, H), voxel_ids, pe_table, params["newline"], side=side, n=n, pool=True, out=x[n_pre:n_pre + n_vis])
+    if pe_mlp is not None:
+        ops.visual_tokens_rows(y.view(frames, tokens, H), pe_rows, params["newline"], side=side, n=n, pool=True, out=x[n_pre:n_pre + n_vis])
+    else:
+        ops.visual_tokens(y.view(frames, tokens, H), voxel_ids, pe_table, params["newline"], side=side, n=n, pool=True, out=x[n_pre:n_pre + n_vis])
     if n_post:
         ops.embed_gather(params["embed"], post_ids, out=x[n_pre + n_vis:])
     if coord_rows is not None and coord_rows.numel():
@@ -612,8 +623,31 @@ def _build_inputs_embeds(params, y, voxel_ids, pe_table, pre_ids, post_ids, fram
     return x, n_pre, n_vis
 
 
+def _pe_mlp_forward(pe_mlp, token_xyz, centres):
+    """Every row that goes through PositionEmbeddingMLP in one sample as ONE batch: the frames * n * n token coordinates, then the centres
+    [k, 3] (Scan2Cap's box centre, or the object proposals' centres; None: none).  The inputs carry no gradient (llava_arch.py:515
+    detaches them).  Returns (pe rows of the tokens, pe rows of the centres, saved)."""
+    xs = token_xyz.reshape(-1, 3)
+    n_tok = xs.shape[0]
+    if centres is not None and centres.numel():
+        xs = torch.cat([xs, centres.reshape(-1, 3).to(xs.dtype)], 0).contiguous()
+    pe, saved = ops.pe_mlp(xs, pe_mlp, want_saved=True)
+    return pe[:n_tok], pe[n_tok:], saved
+
+
+def pe_mlp_backward(dpe, saved, p):
+    """Backward of ops.pe_mlp for dpe [N, H]: the second Linear (linear_backward), the ReLU (v3d_gelu_grad kind 2: h > 0 iff the LayerNorm's
+    output was), the LayerNorm (v3d_layernorm_grad on the rounded z), and the K = 3 first Linear: dw0 on v3d_pe_mlp_wgrad, db0 a column sum.
+    Returns the gradients in p's tree."""
+    x, z, h = saved
+    dh, d_w3, d_b3 = linear_backward(h, p["w3"], dpe, need_db=True)
+    dln = ops.gelu_grad(h, dh, tanh_form=2)
+    dz, d_lnw, d_lnb = ops.layernorm_grad(z, p["ln_w"], dln, 1e-5)
+    return {"w0": ops.pe_mlp_wgrad(dz, x), "b0": ops.colsum(dz), "ln_w": d_lnw, "ln_b": d_lnb, "w3": d_w3, "b3": d_b3}
+
+
 def sample_forward_backward(params, patches, voxel_ids, pe_table, pre_ids, post_ids, labels, rope, frames, n_q, n_kv, hd, tokens=729, side=27, n=14,
-                            coord_rows=None, coord_pe=None, recompute=False):
+                            coord_rows=None, coord_pe=None, recompute=False, pe_mlp=None, pe_centres=None):
     """One training sample end to end on the device (llava_qwen.py:121-205 -> llava_arch.py:336-836 -> modeling_qwen2.py:1145-1217):
     SigLIP tower -> mm_projector -> bilinear pool + 3-D PE + newline rows, spliced between the embedded text rows -> Qwen2 with labels;
     then the backward of all of it.  params: {"vision", "projector": {w1, b1, w2, b2}, "newline" [H], "embed" [vocab, H], "llm"};
@@ -621,20 +655,41 @@ def sample_forward_backward(params, patches, voxel_ids, pe_table, pre_ids, post_
     coordinates: no gradient, llava_arch.py:515), pre_ids / post_ids: the text token ids around <image> (device int64), labels [S];
     coord_rows (device int64) / coord_pe [H]: Scan2Cap's <coord> rows and the box-centre PE added to them.
     recompute: activation re-computation per layer in both towers (the reference's gradient checkpointing, train_multi.sh:72).
+    pe_mlp: the PositionEmbeddingMLP group {w0, b0, ln_w, ln_b, w3, b3} of an `mlp` type; voxel_ids then holds the module's input in the
+    model dtype ([frames, n, n, 3]: the aggregated, with `discrete` voxelised, coordinates), pe_table and coord_pe are not read, and
+    pe_centres [1, 3] is the (voxelised) box centre of the <coord> rows: tokens and centre are encoded as one batch, and the gradients of
+    the token rows and of the summed <coord> rows go back through one backward into grads["pe_mlp"].
     Returns (loss, grads in params' structure; "embed" is a dense [vocab, H] gradient with the text rows' sums)."""
+    if pe_mlp is not None and coord_rows is not None and coord_rows.numel() and (pe_centres is None or pe_centres.numel() != 3):
+        raise V3DError("sample_forward_backward: pe_mlp with <coord> rows needs pe_centres [1, 3], the (voxelised) box centre")
     with _wgrad_overlap(patches.device):
         feat, vsaved = siglip_tower_forward(patches, params["vision"], frames, tokens, recompute)
         pj = params["projector"]
         y, psaved = projector_forward(feat, pj["w1"], pj["b1"], pj["w2"], pj["b2"])
         H = y.shape[1]
-        x, n_pre, n_vis = _build_inputs_embeds(params, y, voxel_ids, pe_table, pre_ids, post_ids, frames, tokens, side, n, coord_rows, coord_pe)
+        pe_rows = None
+        if pe_mlp is not None:
+            has_coord = coord_rows is not None and coord_rows.numel() > 0
+            pe_rows, pe_c, mlp_saved = _pe_mlp_forward(pe_mlp, voxel_ids, pe_centres if has_coord else None)
+            coord_pe = pe_c[0] if has_coord else None
+        x, n_pre, n_vis = _build_inputs_embeds(params, y, voxel_ids, pe_table, pre_ids, post_ids, frames, tokens, side, n, coord_rows, coord_pe,
+                                               pe_mlp, pe_rows)
         loss, dx, llm_grads = llm_forward_backward(params["llm"], x, labels, rope, n_q, n_kv, hd, recompute=recompute)
         d_embed = torch.zeros_like(params["embed"])
         text_rows = torch.cat([torch.arange(n_pre, device=x.device), torch.arange(n_pre + n_vis, x.shape[0], device=x.device)])
-        dfeat, d_newline = inputs_embeds_backward(dx, n_pre, frames, text_rows, torch.cat([pre_ids, post_ids]), d_embed, side=side, n=n)
+        grads = {}
+        if pe_mlp is not None:
+            dfeat, d_newline, dpe = inputs_embeds_backward(dx, n_pre, frames, text_rows, torch.cat([pre_ids, post_ids]), d_embed, side=side, n=n,
+                                                           want_dpe=True)
+            if has_coord:      # the box centre's PE was added to every <coord> row: its gradient is their sum
+                dpe = torch.cat([dpe, ops.colsum(dx[coord_rows].contiguous())[None]], 0).contiguous()
+            grads["pe_mlp"] = pe_mlp_backward(dpe, mlp_saved, pe_mlp)
+        else:
+            dfeat, d_newline = inputs_embeds_backward(dx, n_pre, frames, text_rows, torch.cat([pre_ids, post_ids]), d_embed, side=side, n=n)
         dfeat_in, pgrads = projector_backward(dfeat.view(frames * tokens, H), psaved, pj["w1"], pj["w2"])
         vgrads = siglip_tower_backward(dfeat_in, vsaved, params["vision"], frames, tokens)
-        return loss, {"vision": vgrads, "projector": pgrads, "newline": d_newline, "embed": d_embed, "llm": llm_grads}
+        grads.update({"vision": vgrads, "projector": pgrads, "newline": d_newline, "embed": d_embed, "llm": llm_grads})
+        return loss, grads
 
 
 # ------------------------------------------------------------------------------ ZeRO-2 (scripts/zero2.json:22-34)
@@ -876,7 +931,7 @@ def _bce_head_forward_backward(head_type, gp, obj_feat, query_in, positive, pos_
 
 def ground_sample_forward_backward(params, patches, voxel_ids, pe_table, pre_ids, post_ids, ground_row, obj_mask, box_pe, positive, rope, frames,
                                    n_q, n_kv, hd, temperature=0.07, tokens=729, side=27, n=14, eps=1e-6, recompute=False, head_type="infonce",
-                                   pos_weight=None):
+                                   pos_weight=None, pe_mlp=None, pe_centres=None):
     """A grounding sample of the joint training (llava_qwen.py:121-160 -> predict_box :239-310, object features llava_arch.py:351-376,
     479-501): the same tower -> projector -> splice -> decoder as sample_forward_backward, but the loss is the infonce loss between the
     <ground> token's final hidden state and the object proposals' features (masked means of the projector's patch rows + the box-centre
@@ -888,9 +943,14 @@ def ground_sample_forward_backward(params, patches, voxel_ids, pe_table, pre_ids
     gives them (no zero-target row); "ground" holds {"head": head} ('mlp': Linear, ReLU, LayerNorm, Linear on the query, its output dotted
     with the raw object features) or {"obj", "query", "score": head} ('score': Linear, LayerNorm, ReLU, Linear; the scoring head's w3 is
     [1, 1024], b3 [1]).
+    pe_mlp: the PositionEmbeddingMLP group of an `mlp` type; voxel_ids then holds the module's input in the model dtype, pe_table and
+    box_pe are not read, and pe_centres [n_obj, 3] are the (voxelised) object centres: tokens and centres are encoded as one batch, and the
+    gradient of obj = masked_mean + box_pe with respect to box_pe joins the token rows' in one backward into grads["pe_mlp"].
     Returns (loss, scores f32 [n_obj + 1] ('infonce') or [n_obj], grads) - grads["llm"] has no "lm_head" entry (the LM head takes no part)."""
     if head_type not in GROUND_HEAD_TYPES:
         raise V3DError(f"ground_sample_forward_backward: head_type {head_type!r}, the reference has {GROUND_HEAD_TYPES}")
+    if pe_mlp is not None and (pe_centres is None or pe_centres.numel() != 3 * obj_mask.shape[0]):
+        raise V3DError(f"ground_sample_forward_backward: pe_mlp needs pe_centres [{obj_mask.shape[0]}, 3], the (voxelised) object centres")
     if head_type != "infonce" and pos_weight is None:
         raise V3DError("ground_sample_forward_backward: the BCE heads need pos_weight (ground_bce_targets)")
     with _wgrad_overlap(patches.device):
@@ -898,7 +958,12 @@ def ground_sample_forward_backward(params, patches, voxel_ids, pe_table, pre_ids
         pj, gp = params["projector"], params["ground"]
         y, psaved = projector_forward(feat, pj["w1"], pj["b1"], pj["w2"], pj["b2"])
         H = y.shape[1]
-        x, n_pre, n_vis = _build_inputs_embeds(params, y, voxel_ids, pe_table, pre_ids, post_ids, frames, tokens, side, n)
+        pe_rows = None
+        if pe_mlp is not None:
+            pe_rows, box_pe, mlp_saved = _pe_mlp_forward(pe_mlp, voxel_ids, pe_centres)
+            box_pe = box_pe.contiguous()
+        x, n_pre, n_vis = _build_inputs_embeds(params, y, voxel_ids, pe_table, pre_ids, post_ids, frames, tokens, side, n, pe_mlp=pe_mlp,
+                                               pe_rows=pe_rows)
         h, lsaved = llm_layers_forward(params["llm"], x, rope, n_q, n_kv, hd, eps, recompute)
         # predict_box: the query is the final-norm hidden state of the <ground> row; the objects are masked means of the projector rows
         hq = h[ground_row:ground_row + 1]
@@ -922,10 +987,18 @@ def ground_sample_forward_backward(params, patches, voxel_ids, pe_table, pre_ids
         dx, layer_grads = llm_layers_backward(dh, lsaved, params["llm"], rope, n_q, n_kv, hd, eps)
         d_embed = torch.zeros_like(params["embed"])
         text_rows = torch.cat([torch.arange(n_pre, device=x.device), torch.arange(n_pre + n_vis, x.shape[0], device=x.device)])
-        dfeat, d_newline = inputs_embeds_backward(dx, n_pre, frames, text_rows, torch.cat([pre_ids, post_ids]), d_embed, side=side, n=n)
+        grads = {}
+        if pe_mlp is not None:
+            dfeat, d_newline, dpe = inputs_embeds_backward(dx, n_pre, frames, text_rows, torch.cat([pre_ids, post_ids]), d_embed, side=side, n=n,
+                                                           want_dpe=True)
+            dpe = torch.cat([dpe, d_obj_feat.to(dpe.dtype)], 0).contiguous()          # d obj / d box_pe = d obj
+            grads["pe_mlp"] = pe_mlp_backward(dpe, mlp_saved, pe_mlp)
+        else:
+            dfeat, d_newline = inputs_embeds_backward(dx, n_pre, frames, text_rows, torch.cat([pre_ids, post_ids]), d_embed, side=side, n=n)
         dy = dfeat.view(frames * tokens, H)
         ops.masked_mean_grad(obj_mask, d_obj_feat.contiguous(), dy, accumulate=True)      # the object features' share of the projector rows' gradient
         dfeat_in, pgrads = projector_backward(dy, psaved, pj["w1"], pj["w2"])
         vgrads = siglip_tower_backward(dfeat_in, vsaved, params["vision"], frames, tokens)
-        return loss, scores, {"vision": vgrads, "projector": pgrads, "newline": d_newline, "embed": d_embed,
-                              "llm": {"layers": layer_grads, "norm": d_norm}, "ground": g_ground}
+        grads.update({"vision": vgrads, "projector": pgrads, "newline": d_newline, "embed": d_embed,
+                      "llm": {"layers": layer_grads, "norm": d_norm}, "ground": g_ground})
+        return loss, scores, grads

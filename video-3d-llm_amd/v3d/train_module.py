@@ -16,6 +16,10 @@ Grounding samples (ScanRefer / Multi3DRefer): built with `ground_head_type` ('in
 (`ground_head.N.*`, `ground_head_obj/query/score.N.*`, `ground_head_zero_target`) and `forward_ground(...)` returns the grounding loss
 (`train.ground_sample_forward_backward`) with a `grad_fn`; an LM sample leaves the head's `.grad` untouched, a grounding sample the LM head's.
 
+Position encodings: the shipped `avg-discrete-sin3d` (no parameters) and the learned `mlp` types (`avg[-discrete]-mlp`,
+`sample1[-discrete]-mlp`): the six tensors of `model.world_position_embedding.mlp.{0,1,3}` are parameters of the module (tree["pe_mlp"]) and
+take their `.grad` from LM and grounding samples alike.
+
 One sample per call, as the reference trains (`per_device_train_batch_size 1`, train_multi.sh:58).  Not here: DeepSpeed's engine, LoRA.
 """
 import torch
@@ -23,6 +27,7 @@ import torch.nn as nn
 
 from . import ops, train
 from ._native import V3DError
+from .engine import PE_MLP_KEYS, PE_MLP_PREFIX
 from .token_ids import IGNORE_INDEX, IMAGE_TOKEN_INDEX
 
 VIT = "model.vision_tower.vision_tower.vision_model."
@@ -68,8 +73,9 @@ class _SampleLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, module, args, *flat_params):
-        loss, grads = train.sample_forward_backward(module.param_tree(), *args, recompute=module.recompute)
-        ctx.grads = _match_grads(module, grads, "ground.")          # the grounding head takes no part in an LM sample
+        args, kw = args
+        loss, grads = train.sample_forward_backward(module.param_tree(), *args, recompute=module.recompute, **kw)
+        ctx.grads = _match_grads(module, grads, ("ground.",) + module.unused_prefixes)      # the grounding head takes no part in an LM sample
         return loss.detach().clone()
 
     @staticmethod
@@ -90,8 +96,8 @@ class _SampleLoss(torch.autograd.Function):
 
 
 def _match_grads(module, grads, absent_prefix):
-    """The gradient tree in the module's parameter order; parameters under absent_prefix (the part of the model a sample does not use)
-    may be missing and get no gradient (None: their .grad stays as it was, as under autograd)."""
+    """The gradient tree in the module's parameter order; parameters under absent_prefix (a prefix or a tuple of them: the part of the
+    model a sample does not use) may be missing and get no gradient (None: their .grad stays as it was, as under autograd)."""
     by_name = dict(_flatten(grads))
     missing = set(module.names) - set(by_name)
     if set(by_name) - set(module.names) or any(not n.startswith(absent_prefix) for n in missing):
@@ -106,29 +112,40 @@ class _GroundLoss(_SampleLoss):
     def forward(ctx, module, args, *flat_params):
         args, kw = args
         loss, _, grads = train.ground_sample_forward_backward(module.param_tree(), *args, recompute=module.recompute, **kw)
-        ctx.grads = _match_grads(module, grads, "llm.lm_head")
+        ctx.grads = _match_grads(module, grads, ("llm.lm_head",) + module.unused_prefixes)
         return loss.detach().clone()
 
 
-def _shipped_position_type(wtype):
-    """Raises unless `wtype` parses to the shipped (avg, 1 point, discrete) encoding."""
-    from .loader import parse_position_type
+def _training_position_type(wtype):
+    """-> (pe_kind, aggregation, discrete) of a type training supports: the shipped 'avg-discrete-sin3d', or an `mlp` type
+    (avg / sample1, with or without `discrete`); raises for every other string."""
+    from .loader import parse_mlp_position_type, parse_position_encoder, parse_position_type
+    if parse_position_encoder(wtype) == "mlp":
+        aggregation, _, discrete = parse_mlp_position_type(wtype)
+        return "mlp", aggregation, discrete
     if parse_position_type(wtype) != ("avg", 1, True):
-        raise V3DError(f"world_position_embedding_type {wtype!r}: training supports 'avg-discrete-sin3d' only; the sampled-point, min/max "
-                       "and continuous encodings are inference-only (v3d.engine.Engine)")
+        raise V3DError(f"world_position_embedding_type {wtype!r}: training supports 'avg-discrete-sin3d' and the 'mlp' types "
+                       "('avg[-discrete]-mlp', 'sample1[-discrete]-mlp') only; the sampled-point, min/max and continuous sin3d encodings are "
+                       "inference-only (v3d.engine.Engine)")
+    return "sin3d", "avg", True
 
 
 class LlavaQwenTrainable(nn.Module):
     def __init__(self, tree, n_q, n_kv, head_dim=128, vit_heads=16, vit_inter=4304, rope_theta=1e6, max_pos=8192, recompute=False,
                  min_xyz=(-15, -15, -5), max_xyz=(15, 15, 5), voxel_size=0.1, ground_head_type=None, ground_temperature=0.07,
                  ground_token_ids=None, world_position_embedding_type="avg-discrete-sin3d"):
-        """world_position_embedding_type: the checkpoint's config value; training runs the shipped 'avg-discrete-sin3d' only (the other
-        sin3d types are inference-only: DESIGN section 2) and any other type is refused here, never trained as averages.
+        """world_position_embedding_type: the checkpoint's config value; training runs the shipped 'avg-discrete-sin3d' and the `mlp` types
+        (avg / sample1, with or without `discrete`; tree["pe_mlp"] = {w0, b0, ln_w, ln_b, w3, b3} is then required and trained); the other
+        sin3d types are inference-only and are refused here, never trained as averages.  A "pe_mlp" group in the tree
+        under the sin3d type is carried and gets no gradient.
         ground_head_type: None (no grounding head modelled) or 'infonce' / 'mlp' / 'score' with tree["ground"] in the layout of
         train.ground_sample_forward_backward; ground_temperature: the infonce head's config.ground_head_temperature; ground_token_ids:
         config.ground_token_ids (the label ids whose row is the grounding query, llava_qwen.py:280)."""
         super().__init__()
-        _shipped_position_type(world_position_embedding_type)
+        self.pe_kind, self.aggregation, self.discrete = _training_position_type(world_position_embedding_type)
+        if self.pe_kind == "mlp" and "pe_mlp" not in tree:
+            raise V3DError(f"world_position_embedding_type {world_position_embedding_type!r} but the tree has no 'pe_mlp' entry")
+        self.unused_prefixes = ("pe_mlp.",) if self.pe_kind != "mlp" and "pe_mlp" in tree else ()
         if ground_head_type is not None:
             ground_key_map(ground_head_type)                        # a known type
             if "ground" not in tree:
@@ -146,7 +163,7 @@ class LlavaQwenTrainable(nn.Module):
         self.rope = train.RopeTables(head_dim, max_pos, rope_theta, first.dtype, first.device)
         H = tree["newline"].shape[0]
         n_ids = int(round(max(b - a for a, b in zip(min_xyz, max_xyz)) / voxel_size)) + 1
-        self.pe_table = ops.Sin3DTable(H, n_ids, first.dtype, first.device)
+        self.pe_table = ops.Sin3DTable(H, n_ids, first.dtype, first.device) if self.pe_kind == "sin3d" else None
 
     # ------------------------------------------------------------------ parameter tree <-> nn.Parameters
     def param_tree(self):
@@ -210,6 +227,12 @@ class LlavaQwenTrainable(nn.Module):
                 else:
                     ground.setdefault(mod, {})[leaf] = t(k).contiguous()
             tree["ground"] = ground
+        pe_mlp = "mlp" in kw.get("world_position_embedding_type", "")
+        if pe_mlp:
+            absent = [PE_MLP_PREFIX + k for k in PE_MLP_KEYS.values() if PE_MLP_PREFIX + k not in sd]
+            if absent:
+                raise V3DError(f"world_position_embedding_type {kw['world_position_embedding_type']!r} but the state dict has no {absent[0]}")
+            tree["pe_mlp"] = {leaf: t(PE_MLP_PREFIX + k).contiguous() for leaf, k in PE_MLP_KEYS.items()}
         hd = tree["llm"]["layers"][0]["qkv"].shape[0] // (n_q + 2 * n_kv)
         m = cls(tree, n_q, n_kv, head_dim=hd, vit_heads=vit_heads, vit_inter=sd[VIT + "encoder.layers.0.mlp.fc1.weight"].shape[0],
                 ground_head_type=ground_head_type, **kw)
@@ -218,12 +241,14 @@ class LlavaQwenTrainable(nn.Module):
         # siglip_encoder.py:570-571), the vision_model.head.* pooling head, the ground_head* tensors, rotary inv_freq buffers, ...: kept
         # as they came (frozen, on the host) and emitted unchanged by reference_state_dict(), so that a checkpoint saved through this
         # surface loads strictly on the reference's side
-        m._passthrough = {k: v.detach().clone().cpu() for k, v in sd.items() if k not in m._modelled_keys(n_vit, n_llm, ground_head_type)}
+        m._passthrough = {k: v.detach().clone().cpu() for k, v in sd.items() if k not in m._modelled_keys(n_vit, n_llm, ground_head_type, pe_mlp)}
         return m
 
     @staticmethod
-    def _modelled_keys(n_vit, n_llm, ground_head_type=None):
+    def _modelled_keys(n_vit, n_llm, ground_head_type=None, pe_mlp=False):
         keys = set(ground_key_map(ground_head_type)) if ground_head_type is not None else set()
+        if pe_mlp:
+            keys |= {PE_MLP_PREFIX + k for k in PE_MLP_KEYS.values()}
         keys |= {VIT + "embeddings.patch_embedding.weight", VIT + "embeddings.patch_embedding.bias", VIT + "embeddings.position_embedding.weight",
                 "model.mm_projector.0.weight", "model.mm_projector.0.bias", "model.mm_projector.2.weight", "model.mm_projector.2.bias",
                 "model.image_newline", "model.embed_tokens.weight", "model.norm.weight", "lm_head.weight"}
@@ -275,6 +300,9 @@ class LlavaQwenTrainable(nn.Module):
         if self.ground_head_type is not None:
             for k, (mod, leaf) in ground_key_map(self.ground_head_type).items():
                 out[k] = (tr["ground"][leaf] if mod is None else tr["ground"][mod][leaf]).clone()
+        if self.pe_kind == "mlp":
+            for leaf, k in PE_MLP_KEYS.items():
+                out[PE_MLP_PREFIX + k] = tr["pe_mlp"][leaf].clone()
         for k, v in getattr(self, "_passthrough", {}).items():      # unmodelled tensors of the source checkpoint, unchanged
             out[k] = v.clone()
         return out
@@ -299,18 +327,39 @@ class LlavaQwenTrainable(nn.Module):
         pre_ids, post_ids = ids[:at].to(dev), ids[at + 1:].to(dev)
         full_labels = torch.cat([lab[:at], torch.full((n_vis,), IGNORE_INDEX, dtype=torch.int64), lab[at + 1:]]).to(dev)
         patches = ops.patchify(images.to(device=dev, dtype=dt), 14, tr["vision"]["patch_w"].shape[1])
-        _, _, vox = ops.coord_pool_voxel(world_coords.to(device=dev, dtype=dt), 27, self.min_xyz, self.max_xyz, self.voxel_size, want_avg=False, want_vox=False)
+        vox = self._position_input(world_coords.to(device=dev, dtype=dt))
         coord_rows = coord_pe = None
+        kw = {}
         if coord_token_id is not None and box_input is not None:
             rows = [r if r < at else r + n_vis - 1 for r, t in enumerate(ids.tolist()) if t == coord_token_id]
             if rows:
-                centre = ops.discrete_coords(torch.as_tensor(box_input, dtype=torch.float32).reshape(1, 3).to(device=dev, dtype=dt),
-                                             self.min_xyz, self.max_xyz, self.voxel_size)
-                coord_pe = ops.sin3d_pe(centre[None], tr["newline"].shape[0], dim_t=self.pe_table.dim_t)[0, 0]
+                centre = self._centres(torch.as_tensor(box_input, dtype=torch.float32).reshape(1, 3).to(device=dev, dtype=dt))
+                if self.pe_kind == "mlp":
+                    kw["pe_centres"] = centre          # encoded with the tokens, as one batch
+                else:
+                    coord_pe = ops.sin3d_pe(centre[None], tr["newline"].shape[0], dim_t=self.pe_table.dim_t)[0, 0]
                 coord_rows = torch.tensor(rows, dtype=torch.int64, device=dev)
+        if self.pe_kind == "mlp":
+            kw["pe_mlp"] = tr["pe_mlp"]
         args = (patches, vox, self.pe_table, pre_ids, post_ids, full_labels, self.rope, frames, self.n_q, self.n_kv, self.hd)
         kw_args = args + (729, 27, 14, coord_rows, coord_pe)
-        return _SampleLoss.apply(self, kw_args, *self._params)
+        return _SampleLoss.apply(self, (kw_args, kw), *self._params)
+
+    def _position_input(self, coords):
+        """What the PE is taken of, per token (llava_arch.py:395-420): int32 voxel ids for the shipped type; for an `mlp` type the module's
+        input in the model dtype - the aggregated coordinates, voxelised (integer-valued) with `discrete`."""
+        a = (coords, 27, self.min_xyz, self.max_xyz, self.voxel_size)
+        if self.pe_kind == "sin3d":
+            return ops.coord_pool_voxel(*a, want_avg=False, want_vox=False)[2]
+        if self.aggregation == "avg":
+            avg, vox, _ = ops.coord_pool_voxel(*a, want_avg=not self.discrete, want_vox=self.discrete, want_ids=False)
+        else:
+            avg, vox, _ = ops.coord_points_voxel(coords, self.aggregation, *a[1:], want_pts=not self.discrete, want_vox=self.discrete, want_ids=False)
+        return vox if self.discrete else avg
+
+    def _centres(self, xyz):
+        """Box / object centres [N, 3] as the module takes them: voxelised when the type is `discrete` (llava_arch.py:416-420)."""
+        return ops.discrete_coords(xyz.contiguous(), self.min_xyz, self.max_xyz, self.voxel_size) if self.discrete else xyz.contiguous()
 
     # ------------------------------------------------------------------ grounding samples (llava_qwen.py:239-322)
     def forward_ground(self, input_ids, labels, images, world_coords, boxes, box_labels, ground_token_ids=None):
@@ -342,14 +391,17 @@ class LlavaQwenTrainable(nn.Module):
         pre_ids, post_ids = ids[:at].to(dev), ids[at + 1:].to(dev)
         patches = ops.patchify(images.to(device=dev, dtype=dt), 14, tr["vision"]["patch_w"].shape[1])
         coords = world_coords.to(device=dev, dtype=dt)
-        _, _, vox = ops.coord_pool_voxel(coords, 27, self.min_xyz, self.max_xyz, self.voxel_size, want_avg=False, want_vox=False)
+        vox = self._position_input(coords)
         bx = boxes.to(device=dev, dtype=dt).reshape(-1, 6).contiguous()
         n_obj = bx.shape[0]
         if n_obj < 1:
             raise V3DError("forward_ground: no object proposals")
         mask = ops.object_patch_mask(coords, bx).view(n_obj, -1).contiguous()
-        centres = ops.discrete_coords(bx[:, :3].contiguous(), self.min_xyz, self.max_xyz, self.voxel_size)
-        box_pe = ops.sin3d_pe(centres[None], H, dim_t=self.pe_table.dim_t)[0].contiguous()
+        centres = self._centres(bx[:, :3])
+        if self.pe_kind == "mlp":
+            box_pe = None                              # encoded with the tokens, as one batch (train.ground_sample_forward_backward)
+        else:
+            box_pe = ops.sin3d_pe(centres[None], H, dim_t=self.pe_table.dim_t)[0].contiguous()
         labels0 = [int(i) for i in box_labels]
         kw = {"head_type": self.ground_head_type, "temperature": self.ground_temperature}
         if self.ground_head_type == "infonce":
@@ -357,6 +409,8 @@ class LlavaQwenTrainable(nn.Module):
             positive[torch.tensor(labels0 or [-1], dtype=torch.int64)] = 1        # no target: the zero-target row (llava_qwen.py:304-305)
         else:
             positive, kw["pos_weight"] = train.ground_bce_targets(labels0, n_obj)
+        if self.pe_kind == "mlp":
+            kw["pe_mlp"], kw["pe_centres"] = tr["pe_mlp"], centres
         args = (patches, vox, self.pe_table, pre_ids, post_ids, ground_row, mask, box_pe, positive.to(dev), self.rope, frames,
                 self.n_q, self.n_kv, self.hd)
         return _GroundLoss.apply(self, (args, kw), *self._params)
