@@ -147,10 +147,10 @@ def test_attention_matches_reference_eager_rounding(ops, kind):
 
 @pytest.mark.parametrize("kind", ["bf16", "f16"])
 @pytest.mark.parametrize("Sq,Sk", [(64, 64), (300, 300), (1000, 1000), (2100, 2100), (130, 900), (517, 2048)])
-def test_attention_prefill64_optin_kernel_equals_default_kernel_bitwise(ops, kind, Sq, Sk, monkeypatch):
-    """V3D_ATTN64=1 selects attn_prefill64_kernel (64 queries per wave, 3-deep K/V ring, softmax pieces in the MFMA gaps): same
-    arithmetic in the same order as attn_prefill_kernel, so the outputs are equal bit for bit - causal, GQA, ragged tails,
-    question rows at q_pos0 > 0 over a longer K/V prefix (scene reuse), and the rare max-raise branch (spiked key)."""
+def test_attention_prefill_question_rows_ragged_tails_and_spiked_key(ops, kind, Sq, Sk):
+    """attn_prefill_kernel against the f32 reference: causal, GQA, ragged tails, question rows at q_pos0 > 0 over a longer K/V
+    prefix (scene reuse), and the rare max-raise branch (spiked key).  (These inputs used to compare the retired one-wave-per-SIMD
+    kernel with this one bit for bit: tools/probes/experiments/attention_prefill64_r02.hip.txt.)"""
     dt = DT[kind]
     H, KV, D = 28, 4, 128
     g = torch.Generator().manual_seed(Sq * 7 + Sk)
@@ -160,13 +160,9 @@ def test_attention_prefill64_optin_kernel_equals_default_kernel_bitwise(ops, kin
     if Sk >= 300:
         k[0, Sk - 90, 1] = q[0, Sq - 10, 9] * 30          # a late spike: the running maximum of one query jumps
     q, k, v = q.to(dt).cuda(), k.to(dt).cuda(), v.to(dt).cuda()
-    outs = {}
-    for mode in ("0", "1"):
-        monkeypatch.setenv("V3D_ATTN64", mode)
-        outs[mode] = ops.attention_bshd(q, k, v, causal=True, q_pos0=Sk - Sq)
-    assert torch.equal(outs["0"], outs["1"])
+    got = ops.attention_bshd(q, k, v, causal=True, q_pos0=Sk - Sq)
     want = ref_attention(q.cpu(), k.cpu(), v.cpu(), True, 1 / math.sqrt(D), q_pos0=Sk - Sq)
-    close(outs["1"], want, kind, ulps=4.0, floor=0.3)      # (the spiked row's P is one 16-bit rounding away from one-hot)
+    close(got, want, kind, ulps=4.0, floor=0.3)      # (the spiked row's P is one 16-bit rounding away from one-hot)
 
 
 @pytest.mark.parametrize("kind", ["bf16", "f16"])
@@ -262,32 +258,26 @@ def test_attention_vit_heads_packed_at_true_stride(ops, kind):
 
 @pytest.mark.parametrize("kind", ["bf16", "f16"])
 @pytest.mark.parametrize("B,S", [(32, 729), (3, 729), (1, 729), (5, 256), (2, 128), (40, 729), (7, 200)])
-def test_attention_vit_persistent_kernel_equals_one_workgroup_per_item_bitwise(ops, kind, B, S, monkeypatch):
-    """r04: attn_vit_persistent_kernel (workgroups walk their items; the last step of an item stages the next item's first tiles and
-    loads its Q) = attn_prefill_kernel<96, non-causal, 5 k-steps> (V3D_ATTN_VIT_PERSIST=0), bit for bit: the true shape (32 frames: one
-    (frame, head) pair per workgroup), fewer / more pairs than workgroup slots (3, 1, 40 frames), 4 and 2 key tiles, a short last tile
-    (200 keys), the output columns beyond the 16 x 72 head dims untouched; and against the f32 reference."""
+def test_attention_vit_packed_heads_frame_counts_and_key_tiles(ops, kind, B, S):
+    """attn_prefill_kernel<96, non-causal, 5 k-steps> on the engine's packed layout against the f32 reference: the true shape (32
+    frames), few and many frames (3, 1, 40), 4 and 2 key tiles, a short last tile (200 keys), the output columns beyond the 16 x 72
+    head dims untouched.  (These shapes used to compare the retired persistent kernel with this one bit for bit:
+    tools/probes/experiments/attention_vit_persistent_r04.hip.txt.)"""
     dt = DT[kind]
     H, D, DP = 16, 72, 96
     g = torch.Generator().manual_seed(B * 1000 + S)
     qkv = torch.randn(B * S, 3584, generator=g).to(dt).cuda()
     W = H * D
-
-    def run(mode):
-        monkeypatch.setenv("V3D_ATTN_VIT_PERSIST", mode)
-        att = torch.full((B * S, 1280), 3.0, dtype=dt, device="cuda")
-        ld = qkv.stride(0)
-        ops.attention(qkv, qkv[:, W:], qkv[:, 2 * W:], att, B, S, S, H, H, DP, D, ld, ld, ld, att.stride(0), S * ld, S * ld, S * att.stride(0),
-                      D, D, D, False, 0, D ** -0.5)
-        return att
-    a, b = run("0"), run("1")
-    assert torch.equal(a, b)
-    assert bool((b[:, W:] == 3.0).all())
+    att = torch.full((B * S, 1280), 3.0, dtype=dt, device="cuda")
+    ld = qkv.stride(0)
+    ops.attention(qkv, qkv[:, W:], qkv[:, 2 * W:], att, B, S, S, H, H, DP, D, ld, ld, ld, att.stride(0), S * ld, S * ld, S * att.stride(0),
+                  D, D, D, False, 0, D ** -0.5)
+    assert bool((att[:, W:] == 3.0).all())
     q = qkv[:, :W].view(B, S, H, D).cpu()
     k = qkv[:, W: 2 * W].view(B, S, H, D).cpu()
     v = qkv[:, 2 * W: 3 * W].view(B, S, H, D).cpu()
     want = ref_attention(q, k, v, False, D ** -0.5)
-    close(b[:, :W].view(B, S, H, D), want, kind, ulps=3.0, floor=0.3)
+    close(att[:, :W].view(B, S, H, D), want, kind, ulps=3.0, floor=0.3)
 
 
 @pytest.mark.parametrize("kind", ["bf16", "f16"])

@@ -85,9 +85,7 @@ def test_attention_and_decode_kernels_do_not_spill_in_their_loops(reports):
     assert prefill and all(v <= 24 for v in prefill.values()), prefill
     att = {k: v for k, v in att.items() if k not in prefill}
     assert all(v == 0 for v in reports["attention_bwd.hip"].values()), reports["attention_bwd.hip"]
-    assert all(v == 0 for k, v in att.items() if "attn_prefill64_kernel" in k)
-    # (r04: the opt-in persistent SigLIP attention - V3D_ATTN_VIT_PERSIST=1, measured a tie - carries 6 spilled registers across its item seam)
-    assert all(v <= (8 if "attn_vit_persistent_kernel" in k else 2) for k, v in att.items()), att
+    assert all(v <= 2 for v in att.values()), att
     assert all(v == 0 for v in reports["decode.hip"].values()), reports["decode.hip"]
     out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-fno-slp-vectorize",
                           "-Wno-inline-asm", "-S", "--cuda-device-only", os.path.join(CSRC, "attention.hip"), "-o", "-"], capture_output=True, text=True, timeout=900)
