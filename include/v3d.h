@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define V3D_ABI_VERSION 7   /* 2: *_rows decode entries, fp8 path, a7 / a3 device entries; 3: rope_kv_store, add_row, ...; 4: resize_bicubic, eos_update, embed_grad bounds; 6: sumsq, *_rows entries take 1..32 rows; 7: attention_shared_prefix; ground_scores_rows, add_rows and the v3d_beam_* entries were ADDED under 7 (no entry changed); so were the v3d_sample_* entries, and v3d_coord_points_voxel, v3d_sin3d_table_points_layout, v3d_sin3d_table_build_points, v3d_sin3d_pe_points and v3d_visual_tokens_points; and v3d_pe_mlp_hidden, v3d_visual_tokens_rows, v3d_visual_tokens_rows_grad, v3d_pe_mlp_wgrad_workspace_bytes and v3d_pe_mlp_wgrad */
+#define V3D_ABI_VERSION 7   /* 2: *_rows decode entries, fp8 path, a7 / a3 device entries; 3: rope_kv_store, add_row, ...; 4: resize_bicubic, eos_update, embed_grad bounds; 6: sumsq, *_rows entries take 1..32 rows; 7: attention_shared_prefix; ground_scores_rows, add_rows and the v3d_beam_* entries were ADDED under 7 (no entry changed); so were the v3d_sample_* entries, and v3d_coord_points_voxel, v3d_sin3d_table_points_layout, v3d_sin3d_table_build_points, v3d_sin3d_pe_points and v3d_visual_tokens_points; and v3d_pe_mlp_hidden, v3d_visual_tokens_rows, v3d_visual_tokens_rows_grad, v3d_pe_mlp_wgrad_workspace_bytes and v3d_pe_mlp_wgrad; and v3d_lora_down, v3d_lora_wgrad_chunk, v3d_lora_wgrad_workspace_bytes and v3d_lora_wgrad */
 
 enum { V3D_F32 = 0, V3D_F16 = 1, V3D_BF16 = 2 };
 enum { V3D_U8_HWC = 16 };   /* v3d_resize_bicubic_u8 only: 8-bit interleaved output, no normalisation */
@@ -729,6 +729,32 @@ int v3d_ground_rowdot_bce(const void* x, int64_t ldx, int n, const void* w, int 
  * (one rounding), dq[c] = sum_i dm[i,c] o[i,c] in f32, rows in order.  C a multiple of 8, rows 16-byte aligned. */
 int v3d_mul_rows_grad(const void* dm, int64_t lddm, const void* o, int64_t ldo, const void* q, int n, int C, void* dout, int64_t lddo,
                       void* dq, int dtype, void* stream);
+
+/* ------------------------------------------------------------------ LoRA rank products -- */
+
+/* The products of a LoRA-adapted Linear in which one dimension is the rank (peft's LoraLayer; llava/train/train_3d.py:168-173,
+ * 259-274: lora_r 64, lora_alpha 16 on the decoder's seven linears): for W [N, K], A [r, K], B [N, r], s = lora_alpha / r,
+ *   forward   u = x A^T (rounded), y = x W^T (+ bias) + s u B^T
+ *   backward  du = s dy B (rounded), dB = s dy^T u, dA = du^T x, dx = dy W + du A, no dW.
+ * Both entries take 16-bit operands (V3D_F16 / V3D_BF16), R % 16 == 0 with 16 <= R <= 384 (R = the rank, or the stacked rank of fused
+ * q|k|v and gate|up rows), K % 64 == 0, any M >= 1, row strides that are multiples of 8, 16-byte aligned pointers and operands that span
+ * fewer than 2^31 elements; every argument check runs before any device call.  Nothing outside [M, R] resp. [R, K] of the outputs is
+ * written and nothing outside [M, K], [R, K], [M, R] of the operands is read.
+ *
+ * v3d_lora_down: out[M, R] = T(scale * X[M, K] . P[R, K]^T), f32 accumulation with k ascending in one run per output, one f32 product
+ * with scale, one rounding.  u = x A^T (P = A, scale 1) and du = s dy B (P = B^T [r, N], a transposed copy by v3d_transpose). */
+int v3d_lora_down(const void* X, int64_t ldx, const void* P, int64_t ldp, float scale, void* out, int64_t ldo, int64_t M, int R, int K,
+                  int dtype, void* stream);
+/* v3d_lora_wgrad: G[R, K] = scale * U[M, R]^T . X[M, K] in g_dtype (f32, or 16 bit with one rounding); the sum runs over the M rows and
+ * both operands are read as stored.  dA = du^T x (U = du, X = x) and dB^T = s u^T dy (U = u, X = dy, scale s).  The rows are cut into
+ * chunks of v3d_lora_wgrad_chunk(M, R, K) rows (a multiple of 32); each workgroup sums one chunk in row order for 64 columns and stores
+ * an f32 partial into workspace, and a second launch adds the partials in chunk order, multiplies by scale and rounds: no atomics, two
+ * calls give identical bits.  workspace: v3d_lora_wgrad_workspace_bytes(M, R, K) bytes from the caller (both are pure functions of the
+ * shape, host only, 0 for a shape the kernel does not take; neither decreases when M grows). */
+int64_t v3d_lora_wgrad_chunk(int64_t M, int R, int K);
+int64_t v3d_lora_wgrad_workspace_bytes(int64_t M, int R, int K);
+int v3d_lora_wgrad(const void* U, int64_t ldu, const void* X, int64_t ldx, float scale, void* G, int64_t ldg, int g_dtype, int64_t M, int R,
+                   int K, int dtype, float* workspace, void* stream);
 
 /* ------------------------------------------------------------------ host helpers -------- */
 

@@ -86,9 +86,13 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
     # ------------------------------------------------------------------ loading (builder.py:206-228)
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, config=None, torch_dtype=None, dtype=None, device_map=None,
-                        low_cpu_mem_usage=None, attn_implementation=None, llm_fp8=False, max_frames=32, llm_fp4=False, **kwargs):
+                        low_cpu_mem_usage=None, attn_implementation=None, llm_fp8=False, max_frames=32, llm_fp4=False, lora_path=None,
+                        **kwargs):
         """low_cpu_mem_usage / attn_implementation are accepted and have no effect here (weights go straight to HBM; attention
-        is the engine's flash kernel whatever the name says).  Quantised / sharded-device loading is refused."""
+        is the engine's flash kernel whatever the name says).  Quantised / sharded-device loading is refused.
+        lora_path: a LoRA adapter directory (adapter_config.json, adapter_model.bin, non_lora_trainables.bin) merged into the decoder's
+        linears on the device, W' = round(W + round(s B A)), before the engine lays the weights out and before llm_fp8 / llm_fp4
+        quantise them (model_scanqa.py:103-112: PeftModel.from_pretrained -> merge_and_unload -> non_lora_trainables)."""
         for k in ("load_in_8bit", "load_in_4bit", "quantization_config"):
             if kwargs.pop(k, None):
                 raise NotImplementedError(f"{k}: bitsandbytes quantisation is outside the accelerated path (use llm_fp8=True for e4m3 or llm_fp4=True for MXFP4 weights)")
@@ -112,6 +116,8 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
             if not tower_dir or not os.path.isdir(tower_dir):
                 raise V3DError(f"the checkpoint holds no vision tower and config.mm_vision_tower = {tower_dir!r} is not a local directory")
             sd.update(loader.drop_deleted_tower_layer(loader.read_tower_weights(tower_dir), True))
+        if lora_path is not None:
+            sd = loader.merge_lora(sd, loader.load_lora(os.fspath(lora_path)), dt, _device_of(device_map))
         if "lm_head.weight" not in sd:                 # tie_word_embeddings checkpoints store the table once
             if not getattr(config, "tie_word_embeddings", False):
                 raise V3DError("the checkpoint holds no lm_head.weight and config.tie_word_embeddings is not set")

@@ -253,6 +253,7 @@ def main(argv=None, task=None):
     ap.add_argument("--loader-workers", type=int, default=0)
     ap.add_argument("--shard", choices=("stride", "scene"), default=None)
     ap.add_argument("--llm-weights", choices=E.LLM_WEIGHTS, default="bf16", help="decoder linears: 16-bit (default), e4m3 (fp8) or MXFP4 (fp4); not reference paths")
+    ap.add_argument("--lora-path", default=None, help="a LoRA adapter directory merged into the decoder at load (every task)")
     ap.add_argument("--n_gpu", type=int, default=None, help="the reference's flag: started plainly with N > 1, launch N ranks of this runner")
     E.add_beam_arguments(ap)
     E.add_sampling_arguments(ap)
@@ -283,7 +284,8 @@ def main(argv=None, task=None):
         pool = frame_io.make_pool(a.loader_workers or E.default_workers())          # forked before this process touches the GPU
     rank, world, dev, gather_dev = E.rank_setup(a.n_gpu)
     from llava.video_utils import VideoProcessor
-    tokenizer, model, image_processor, name = E.load_model(os.path.expanduser(a.model_path), a.overwrite_cfg, a.llm_weights)
+    tokenizer, model, image_processor, name = E.load_model(os.path.expanduser(a.model_path), a.overwrite_cfg, a.llm_weights,
+                                                              os.path.expanduser(a.lora_path) if a.lora_path else None)
     vp = VideoProcessor(video_folder=a.video_folder, annotation_dir=a.embodiedscan_folder, frame_sampling_strategy=a.frame_sampling_strategy,
                         metadata_dir=a.metadata_folder)
     times = []

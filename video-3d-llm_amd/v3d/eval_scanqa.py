@@ -409,11 +409,12 @@ def add_beam_arguments(ap):
     ap.add_argument("--length_penalty", type=float, default=1.0, help="beam search: a finished hypothesis scores sum(log p) / n ** length_penalty")
 
 
-def load_model(model_path, overwrite_cfg=False, llm_weights="bf16"):
+def load_model(model_path, overwrite_cfg=False, llm_weights="bf16", lora_path=None):
     """load_pretrained_model (llava/model/builder.py) - the reference's own loader when its checkout is importable behind the
     overlay, else the same call sequence from v3d.loader.  llm_weights "fp8" / "fp4" (e4m3 / MXFP4
     decoder linears, Engine(llm_fp8=) / Engine(llm_fp4=); not reference paths) always load through v3d.loader: the reference's
-    loader has no such switch."""
+    loader has no such switch.  lora_path: a LoRA adapter directory merged into the decoder's linears at load (model_scanqa.py:91-112), also
+    through v3d.loader - the merge runs on the device, before the engine lays the weights out and before llm_weights quantises them."""
     if llm_weights not in LLM_WEIGHTS:
         raise ValueError(f"llm_weights {llm_weights!r}: one of {LLM_WEIGHTS}")
     from llava.mm_utils import get_model_name_from_path
@@ -423,9 +424,10 @@ def load_model(model_path, overwrite_cfg=False, llm_weights="bf16"):
         from llava.model.builder import load_pretrained_model
     except ImportError:
         from .loader import load_pretrained_model
-    if llm_weights != "bf16":
+    if llm_weights != "bf16" or lora_path is not None:
         from .loader import load_pretrained_model as load_quantised
-        tokenizer, model, image_processor, _ = load_quantised(model_path, None, name, overwrite_config=overwrite, llm_weights=llm_weights)
+        tokenizer, model, image_processor, _ = load_quantised(model_path, None, name, overwrite_config=overwrite, llm_weights=llm_weights,
+                                                              lora_path=lora_path)
         return tokenizer, model, image_processor, name
     tokenizer, model, image_processor, _ = load_pretrained_model(model_path, None, name, overwrite_config=overwrite)
     return tokenizer, model, image_processor, name
@@ -453,6 +455,8 @@ def main(argv=None):
                     help="stride: questions[rank::world] (the reference); scene: whole scenes per rank (default with --reuse-scenes)")
     ap.add_argument("--llm-weights", choices=LLM_WEIGHTS, default="bf16",
                     help="decoder linears: 16-bit as the checkpoint stores them (default), OCP e4m3 (fp8) or OCP MXFP4 (fp4); the last two are not reference paths")
+    ap.add_argument("--lora-path", default=None,
+                    help="a LoRA adapter directory (adapter_config.json, adapter_model.bin, non_lora_trainables.bin) merged into the decoder at load")
     ap.add_argument("--n_gpu", type=int, default=None,
                     help="the reference's flag (model_scanqa.py:222): started plainly with N > 1, launch N ranks of this runner on this node")
     add_beam_arguments(ap)
@@ -474,7 +478,8 @@ def main(argv=None):
         pool = frame_io.make_pool(a.loader_workers or default_workers())        # forked before this process touches the GPU
     rank, world, dev, gather_dev = rank_setup(a.n_gpu)
     from llava.video_utils import VideoProcessor
-    tokenizer, model, image_processor, name = load_model(os.path.expanduser(a.model_path), a.overwrite_cfg, a.llm_weights)
+    tokenizer, model, image_processor, name = load_model(os.path.expanduser(a.model_path), a.overwrite_cfg, a.llm_weights,
+                                                            os.path.expanduser(a.lora_path) if a.lora_path else None)
     vp = VideoProcessor(video_folder=a.video_folder, annotation_dir=a.embodiedscan_folder, frame_sampling_strategy=a.frame_sampling_strategy,
                         metadata_dir=a.metadata_folder)
     times = []

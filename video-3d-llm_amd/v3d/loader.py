@@ -158,19 +158,144 @@ def drop_deleted_tower_layer(sd, tower_from_raw_siglip):
     return {k: v for k, v in sd.items() if not k.startswith(f"{pfx}{last}.")}
 
 
+# ------------------------------------------------------------------------------ LoRA adapter directories (--lora-path)
+
+LORA_TARGETS = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")     # find_all_linear_names for this model
+_LORA_PARENT = {"q_proj": "self_attn", "k_proj": "self_attn", "v_proj": "self_attn", "o_proj": "self_attn", "gate_proj": "mlp",
+                "up_proj": "mlp", "down_proj": "mlp"}
+
+
+def strip_peft_prefix(key):
+    """builder.py:104-106: `base_model.` off, then `model.` off a key that starts `model.model.` - peft's wrapper names down to the
+    state dict's."""
+    if key.startswith("base_model."):
+        key = key[len("base_model."):]
+    if key.startswith("model.model."):
+        key = key[len("model."):]
+    return key
+
+
+def lora_key(layer, module, which, adapter_name=None):
+    """The reference's key of one adapter matrix: base_model.model.model.layers.{i}.{self_attn|mlp}.{module}.lora_{A|B}[.name].weight."""
+    mid = f".{adapter_name}" if adapter_name else ""
+    return f"base_model.model.model.layers.{layer}.{_LORA_PARENT[module]}.{module}.lora_{which}{mid}.weight"
+
+
+def save_lora(lora_dir, adapters, non_lora_trainables, r, lora_alpha):
+    """An adapter directory as the reference's trainer leaves it (train_3d.py:1875-1884): adapter_config.json, adapter_model.bin
+    (torch.save; keys lora_key(...)) and non_lora_trainables.bin (the trained non-adapter tensors under the reference's keys).
+    adapters: {(layer, module): (A [r, K], B [N, r])}."""
+    os.makedirs(lora_dir, exist_ok=True)
+    cfg = {"peft_type": "LORA", "r": int(r), "lora_alpha": lora_alpha, "target_modules": list(LORA_TARGETS), "lora_dropout": 0.0,
+           "bias": "none", "task_type": "CAUSAL_LM"}
+    with open(os.path.join(lora_dir, "adapter_config.json"), "w") as f:
+        json.dump(cfg, f, indent=1)
+    sd = {}
+    for (layer, module), (a, b) in sorted(adapters.items()):
+        sd[lora_key(layer, module, "A")] = a.detach().cpu().contiguous()
+        sd[lora_key(layer, module, "B")] = b.detach().cpu().contiguous()
+    torch.save(sd, os.path.join(lora_dir, "adapter_model.bin"))
+    torch.save({k: v.detach().cpu().contiguous() for k, v in non_lora_trainables.items()}, os.path.join(lora_dir, "non_lora_trainables.bin"))
+
+
+def load_lora(lora_dir):
+    """Reads an adapter directory -> {"r", "lora_alpha", "scaling", "adapters": {(layer, module): (A, B)}, "non_lora": {key: tensor}}.
+    Keys in either form peft writes (`.lora_A.weight`, or `.lora_A.<adapter name>.weight` as the drivers' adapter_name="lora" gives),
+    prefixes stripped as builder.py:104-106 does.  lora_dropout is accepted whatever it is (it plays no part in a merge); bias must be
+    "none"."""
+    import re
+    cp = os.path.join(lora_dir, "adapter_config.json")
+    if not os.path.exists(cp):
+        raise V3DError(f"{lora_dir} holds no adapter_config.json: not a LoRA adapter directory")
+    with open(cp) as f:
+        cfg = json.load(f)
+    if cfg.get("peft_type", "LORA") != "LORA":
+        raise V3DError(f"adapter_config.peft_type = {cfg.get('peft_type')!r}: only LORA adapters can be merged")
+    if cfg.get("bias", "none") != "none":
+        raise V3DError(f"adapter_config.bias = {cfg.get('bias')!r}: adapter biases are not built, lora_bias must be 'none'")
+    r, alpha = int(cfg["r"]), float(cfg["lora_alpha"])
+    for name in ("adapter_model.safetensors", "adapter_model.bin"):
+        if os.path.exists(os.path.join(lora_dir, name)):
+            raw = _load_file(os.path.join(lora_dir, name))
+            break
+    else:
+        raise V3DError(f"{lora_dir} holds no adapter_model.safetensors / adapter_model.bin")
+    pat = re.compile(r"^model\.layers\.(\d+)\.(?:self_attn|mlp)\.([a-z_]+)\.lora_([AB])(?:\.[^.]+)?\.weight$")
+    parts = {}
+    for k, v in raw.items():
+        m = pat.match(strip_peft_prefix(k))
+        if m is None or m.group(2) not in LORA_TARGETS:
+            raise V3DError(f"adapter key {k!r}: adapters are merged on the decoder's {', '.join(LORA_TARGETS)} only")
+        parts.setdefault((int(m.group(1)), m.group(2)), {})[m.group(3)] = v
+    adapters = {}
+    for key, ab in parts.items():
+        if sorted(ab) != ["A", "B"] or ab["A"].shape[0] != r or ab["B"].shape[1] != r:
+            raise V3DError(f"adapter of layer {key[0]} {key[1]}: needs lora_A [r, in] and lora_B [out, r] with r = {r}")
+        adapters[key] = (ab["A"], ab["B"])
+    nl = os.path.join(lora_dir, "non_lora_trainables.bin")
+    non_lora = {strip_peft_prefix(k): v for k, v in _load_file(nl).items()} if os.path.exists(nl) else {}
+    return {"r": r, "lora_alpha": alpha, "scaling": alpha / r, "adapters": adapters, "non_lora": non_lora}
+
+
+def merge_lora(sd, lora, dtype, device):
+    """Merges every adapter of load_lora's result into the state dict's 16-bit weight on the device, W' = round(W + round(s B A))
+    (v3d.train.lora_merge: one v3d_gemm with EPI_RES per linear), then overlays the non-adapter tensors.  Runs before the
+    engine lays the weights out and before any e4m3 / MXFP4 quantisation; the merged tensors stay in HBM."""
+    from . import train
+    out = dict(sd)
+    for (layer, module), (a, b) in sorted(lora["adapters"].items()):
+        key = f"model.layers.{layer}.{_LORA_PARENT[module]}.{module}.weight"
+        if key not in out:
+            raise V3DError(f"the adapter names {key}, which the checkpoint does not have")
+        w = out[key].to(device=device, dtype=dtype).contiguous()
+        if tuple(w.shape) != (b.shape[0], a.shape[1]):
+            raise V3DError(f"adapter of {key}: A {tuple(a.shape)} / B {tuple(b.shape)} do not fit the weight {tuple(w.shape)}")
+        out[key] = train.lora_merge(w, _pad_rank(a.to(device=device, dtype=dtype), 0), _pad_rank(b.to(device=device, dtype=dtype), 1), lora["scaling"])
+    for k, v in lora["non_lora"].items():
+        out[k] = v
+    return out
+
+
+def _pad_rank(t, dim):
+    """Zero rows (A) / columns (B) up to the next multiple of 16 (v3d_transpose takes columns in eights); zeros add nothing to B A."""
+    r = t.shape[dim]
+    rp = (r + 15) // 16 * 16
+    if rp == r:
+        return t.contiguous()
+    shape = list(t.shape)
+    shape[dim] = rp
+    out = torch.zeros(shape, dtype=t.dtype, device=t.device)
+    out.narrow(dim, 0, r).copy_(t)
+    return out
+
+
 def load_pretrained_model(model_path, model_base=None, model_name=None, device_map="auto", torch_dtype="float16",
-                          attn_implementation="flash_attention_2", overwrite_config=None, llm_weights="bf16", **kwargs):
+                          attn_implementation="flash_attention_2", overwrite_config=None, llm_weights="bf16", lora_path=None, **kwargs):
     """The LLaVA-Qwen branch of llava.model.builder.load_pretrained_model (builder.py:26-36, 206-228, 266-292) for callers that
     run without the reference checkout on the path: tokenizer, LlavaQwenForCausalLM.from_pretrained with the same keyword
     arguments, resize_token_embeddings, the tower's image processor, the context length.  Same return tuple.  llm_weights "fp8" / "fp4":
-    e4m3 / MXFP4 decoder linears (Engine(llm_fp8=) / Engine(llm_fp4=)); the reference has neither."""
+    e4m3 / MXFP4 decoder linears (Engine(llm_fp8=) / Engine(llm_fp4=)); the reference has neither.  lora_path: an adapter directory
+    (model_scanqa.py:91-112): its config.json (when it has one) overwrites the checkpoint's config and its tokenizer (when it has one)
+    replaces the checkpoint's; inside from_pretrained the adapters are merged on the device and non_lora_trainables.bin is overlaid, then
+    llm_weights quantises the merged 16-bit weights; the token tables are resized to the tokenizer last (the reference's drivers resize
+    before they merge: the merge touches only the decoder's linears, which a resize does not)."""
     from transformers import AutoTokenizer
 
     from llava.model import LlavaQwenConfig, LlavaQwenForCausalLM
     if model_base is not None or kwargs:
         raise NotImplementedError(f"only a full LLaVA-Qwen checkpoint directory is supported here (model_base / {sorted(kwargs)} given)")
     dt = {"float16": torch.float16, "bfloat16": torch.bfloat16}[torch_dtype] if isinstance(torch_dtype, str) else torch_dtype
-    tokenizer = AutoTokenizer.from_pretrained(model_path)
+    tok_dir = model_path
+    if lora_path is not None:
+        lora_path = os.fspath(lora_path)
+        cj = os.path.join(lora_path, "config.json")
+        if os.path.exists(cj):
+            with open(cj) as f:
+                from_lora = {k: v for k, v in json.load(f).items() if not k.startswith("_") and k not in ("transformers_version", "architectures")}
+            overwrite_config = {**from_lora, **(overwrite_config or {})}
+        if os.path.exists(os.path.join(lora_path, "tokenizer_config.json")):
+            tok_dir = lora_path
+    tokenizer = AutoTokenizer.from_pretrained(tok_dir)
     cfg = None
     if overwrite_config:
         cfg = LlavaQwenConfig.from_pretrained(model_path)
@@ -178,7 +303,7 @@ def load_pretrained_model(model_path, model_base=None, model_name=None, device_m
             setattr(cfg, k, v)
     model = LlavaQwenForCausalLM.from_pretrained(model_path, low_cpu_mem_usage=True, attn_implementation=attn_implementation, config=cfg,
                                                  device_map=device_map, torch_dtype=dt, llm_fp8=llm_weights == "fp8",
-                                                 llm_fp4=llm_weights == "fp4")
+                                                 llm_fp4=llm_weights == "fp4", lora_path=lora_path)
     # builder.py:266-275: the image patch / start / end tokens join the tokenizer before the tables are resized to len(tokenizer)
     # (mm_use_im_patch_token defaults to True upstream) - mirrored so that both loaders see the same vocabulary size
     if getattr(model.config, "mm_use_im_patch_token", True):

@@ -1395,6 +1395,60 @@ def colsum(x, dtype=None):
     return out
 
 
+def _rows_2d(t, name):
+    """A 16-bit device matrix as the kernels take it: unit column stride, any row stride (a column slice of a wider buffer stays a view)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise V3DError(f"{name} must be a CUDA/HIP tensor resident in HBM; there is no CPU path")
+    if t.dim() != 2 or t.dtype not in (torch.float16, torch.bfloat16):
+        raise V3DError(f"{name} must be a 16-bit matrix (got {tuple(t.shape)} {t.dtype})")
+    return t if t.stride(1) == 1 and t.shape[0] > 0 and (t.shape[0] == 1 or t.stride(0) >= t.shape[1]) else t.contiguous()
+
+
+def lora_down(x, p, scale=1.0, out=None):
+    """out [M, R] = round(scale * x [M, K] . p [R, K]^T) (v3d_lora_down): u = x A^T of a LoRA linear, and du = s dy B against the
+    transposed copy of B.  R % 16 == 0 up to 384, K % 64 == 0."""
+    x, p = _rows_2d(x, "x"), _rows_2d(p, "p")
+    M, K = x.shape
+    R = p.shape[0]
+    if p.shape[1] != K or p.dtype != x.dtype:
+        raise V3DError(f"lora_down: p must be [R,{K}] {x.dtype} (got {tuple(p.shape)} {p.dtype})")
+    if out is None:
+        out = torch.empty((M, R), dtype=x.dtype, device=x.device)
+    _rows_fit(out, M, R, x.dtype, "lora_down")
+    ldo = out.stride(0) if out.dim() == 2 else R
+    check(lib().v3d_lora_down(_p(x), x.stride(0), _p(p), p.stride(0), float(scale), _p(out), ldo, M, R, K, _code(x), _stream()), "v3d_lora_down")
+    return out
+
+
+def lora_wgrad_workspace(M, R, K, device):
+    """The f32 partial slabs of lora_wgrad for this shape (v3d_lora_wgrad_workspace_bytes): allocate once, outside the step."""
+    n = lib().v3d_lora_wgrad_workspace_bytes(M, R, K)
+    if n <= 0:
+        raise V3DError(f"lora_wgrad: no kernel for M={M} R={R} K={K} (R % 16 == 0 up to 384, K % 64 == 0)")
+    return torch.empty(n // 4, dtype=torch.float32, device=device)
+
+
+def lora_wgrad(u, x, scale=1.0, dtype=None, out=None, workspace=None):
+    """g [R, K] = scale * u [M, R]^T . x [M, K], summed over the M rows in a fixed order (v3d_lora_wgrad; the chunk is
+    v3d_lora_wgrad_chunk rows): dA = du^T x, and dB^T = s u^T dy.  g in `dtype` (default f32: the gradient of an f32 master)."""
+    u, x = _rows_2d(u, "u"), _rows_2d(x, "x")
+    M, R = u.shape
+    K = x.shape[1]
+    if x.shape[0] != M or x.dtype != u.dtype:
+        raise V3DError(f"lora_wgrad: x must be [{M},K] {u.dtype} (got {tuple(x.shape)} {x.dtype})")
+    if workspace is None:
+        workspace = lora_wgrad_workspace(M, R, K, u.device)
+    elif workspace.dtype != torch.float32 or workspace.numel() * 4 < lib().v3d_lora_wgrad_workspace_bytes(M, R, K):
+        raise V3DError("lora_wgrad: workspace must be f32 with at least v3d_lora_wgrad_workspace_bytes(M, R, K) bytes")
+    gd = dtype or torch.float32
+    if out is None:
+        out = torch.empty((R, K), dtype=gd, device=u.device)
+    _rows_fit(out, R, K, gd, "lora_wgrad")
+    check(lib().v3d_lora_wgrad(_p(u), u.stride(0), _p(x), x.stride(0), float(scale), _p(out), out.stride(0), _DT[gd], M, R, K, _code(u),
+                               _p(workspace), _stream()), "v3d_lora_wgrad")
+    return out
+
+
 def rmsnorm_grad(x, weight, dy, eps=1e-6, add=None, dw_dtype=None):
     """Backward of rmsnorm: returns (dx [rows, cols] (+ add), dweight [cols])."""
     x, dy = _dev(x, "x"), _dev(dy, "dy")

@@ -21,7 +21,8 @@ write an [S, S] matrix (v3d_attention_backward, csrc/attention_bwd.hip - the def
 products on v3d_gemm), kept as an independent cross-check.  Parity: tests/test_gpu_train_dense.py, tests/test_gpu_zero2.py (autograd in
 f32 over the reference's formulae).  ground_sample_forward_backward is the grounding samples' step over object proposals, for all three
 head types of llava_qwen.py:57-110: 'infonce' (the shipped checkpoints' loss), 'mlp' and 'score' (BCE with positive weighting, :313-322).
-Not here: LoRA; the HF Trainer surface is v3d.train_module."""
+LoRA on the decoder's linears: lora_init / lora_linear_* below; every step function runs layers that carry adapters by the LoRA rule and
+takes frozen= (names whose leaves are not trained).  The HF Trainer surface is v3d.train_module."""
 import math
 import os
 
@@ -143,18 +144,307 @@ def linear_backward(x, w, dy, res=None, need_dx=True, need_dw=True, need_db=Fals
     return dx, dw, db
 
 
-def mlp_block_forward(h, ln_w, w_gate_up, w_down, eps=1e-6):
+# ------------------------------------------------------------------------------ LoRA on a frozen Linear
+#
+# For W [N, K] (frozen), A [R, K], B [N, R], s = lora_alpha / r (peft's LoraLayer; train_3d.py:168-173 lora_r 64, lora_alpha 16):
+#     forward   u = round(x A^T);   y = round(round(x W^T (+ bias) (+ res)) + round(u (s B)^T))
+#     backward  du = round(s dy B); dA = du^T x;  dB = s dy^T u;  dx = round(round(dy W (+ res)) + round(du A));  no dW.
+# u, du (against the transposed copy of B), dA and dB^T each take the faster of the rank kernel (v3d_lora_down, v3d_lora_wgrad) and the
+# existing GEMM with the rank padded to 128 (the dispatch and its measurements: below LoraState), and
+# the two products whose k dimension is the rank on v3d_gemm with the base product's output as the EPI_RES residual, written to a second
+# buffer (res never aliases out).  The rank is padded to a multiple of 128 with zero columns for them.  In the training layouts q|k|v
+# and gate|up are fused rows; their adapters are STACKED: A's rows concatenated (R = 3 r, 2 r), B block-diagonal, its off-diagonal
+# blocks identically zero and never updated (lora_mask_grads).  With B = 0 (peft's init) u (s B)^T and du are exact zeros: y and dx are
+# bit-identical to the base Linear's and dA == 0.
+LORA_LINEARS = ("qkv", "o", "gate_up", "down")                            # the fused linears of a decoder layer that take adapters
+LORA_MODULES = {"qkv": ("q_proj", "k_proj", "v_proj"), "o": ("o_proj",), "gate_up": ("gate_proj", "up_proj"), "down": ("down_proj",)}
+
+
+def lora_stack(a_list, b_list):
+    """Per-module A_i [r, K], B_i [N_i, r] -> (A [sum r, K], B [sum N_i, sum r] block-diagonal, blocks [(row0, row1, col0, col1)])."""
+    A = torch.cat(list(a_list), 0)
+    B = torch.zeros((sum(b.shape[0] for b in b_list), A.shape[0]), dtype=b_list[0].dtype, device=b_list[0].device)
+    blocks, r0, c0 = [], 0, 0
+    for a, b in zip(a_list, b_list):
+        if b.shape[1] != a.shape[0]:
+            raise V3DError(f"lora_stack: B {tuple(b.shape)} does not match A {tuple(a.shape)}")
+        B[r0:r0 + b.shape[0], c0:c0 + a.shape[0]] = b
+        blocks.append((r0, r0 + b.shape[0], c0, c0 + a.shape[0]))
+        r0, c0 = r0 + b.shape[0], c0 + a.shape[0]
+    return A, B, blocks
+
+
+def lora_unstack(A, B, blocks):
+    """The inverse of lora_stack; refuses a B whose off-diagonal blocks are not identically zero (it would not be a set of per-module
+    adapters)."""
+    mask = torch.zeros(B.shape, dtype=torch.bool, device=B.device)
+    for r0, r1, c0, c1 in blocks:
+        mask[r0:r1, c0:c1] = True
+    if bool((B[~mask] != 0).any()):
+        raise V3DError("lora_unstack: an off-diagonal block of the stacked B is not zero")
+    return [A[c0:c1].clone() for _, _, c0, c1 in blocks], [B[r0:r1, c0:c1].clone() for r0, r1, c0, c1 in blocks]
+
+
+class LoraState:
+    """What the products need beside the trained leaves A, B of one adapted Linear: s, the block structure, and derived 16-bit copies
+    of a few MB, all with the rank zero-padded to Rp (a multiple of 128) - (s B) [N, Rp], A^T [K, Rp], A [Rp, K], (s B)^T [Rp, N] and
+    B^T [R, N] - refreshed from the leaves after every optimizer step (refresh)."""
+
+    def __init__(self, leaves, s, blocks=None):
+        A, B = leaves["A"], leaves["B"]
+        if A.dim() != 2 or B.dim() != 2 or B.shape[1] != A.shape[0] or A.dtype != B.dtype:
+            raise V3DError(f"LoraState: A {tuple(A.shape)} / B {tuple(B.shape)} do not form an adapter")
+        self.s, self.R, self.Rp = float(s), A.shape[0], _pad(A.shape[0], 128)
+        self.blocks = blocks or [(0, B.shape[0], 0, A.shape[0])]
+        N, K = B.shape[0], A.shape[1]
+        self.sB = torch.zeros((N, self.Rp), dtype=B.dtype, device=B.device)
+        self.Bt = torch.empty((self.R, _pad(N, 8)), dtype=B.dtype, device=B.device)
+        self.At = torch.empty((K, self.Rp), dtype=A.dtype, device=A.device)
+        self.Ap = torch.zeros((self.Rp, K), dtype=A.dtype, device=A.device)
+        self.sBtp = torch.zeros((self.Rp, _pad(N, 8)), dtype=B.dtype, device=B.device)
+        self.refresh(leaves)
+
+    def refresh(self, leaves):
+        A, B = leaves["A"], leaves["B"]
+        self.sB[:, :self.R] = (B.float() * self.s).to(B.dtype)            # one rounding of s B (exact when s is a power of two)
+        ops.transpose(B, out_cols=self.Bt.shape[1], out=self.Bt)          # [R, N]
+        ops.transpose(A, out_cols=self.Rp, out=self.At)                   # [K, Rp], columns >= R zero
+        self.Ap[:self.R] = A
+        ops.transpose(self.sB[:, :self.R], out_cols=self.sBtp.shape[1], out=self.sBtp[:self.R])
+
+
+# Which route each rank product takes (measured on one MI355X at S = 6794, r = 64, profiles/lora.txt; DESIGN.md section 7):
+#   down   v3d_gemm with the rank padded to 128 output columns beats v3d_lora_down at every shape of the decoder (the kernel takes x 1.28 .. 1.51
+#          of its time), so it is the default; V3D_LORA_DOWN=kernel selects the kernel.
+#   wgrad  v3d_lora_wgrad takes a third of v3d_gemm_layout(1, 1)'s time at K <= 4608 (x 0.32 .. 0.36) and loses at K = 18944 / 37888
+#          (x 1.02 / 1.25): the kernel up to LORA_WGRAD_MAX_K columns, the GEMM above; V3D_LORA_WGRAD=kernel / gemm forces one.
+LORA_WGRAD_MAX_K = 8192
+
+
+def _down_on_kernel():
+    return os.environ.get("V3D_LORA_DOWN", "gemm") == "kernel"
+
+
+def _wgrad_on_kernel(K, dtype, x_dtype):
+    if K % 128 != 0 or dtype != x_dtype:                                  # the GEMM needs K % 128 == 0 and writes the operands' dtype
+        return True
+    mode = os.environ.get("V3D_LORA_WGRAD", "auto")
+    if mode in ("kernel", "gemm"):
+        return mode == "kernel"
+    return K <= LORA_WGRAD_MAX_K
+
+
+def lora_down(x, p_kernel, p_padded, scale, R, Rp):
+    """[M, Rp] = x p^T, columns >= R zero: p_kernel [R, K] (scale applied by the kernel) or p_padded [Rp, K] with scale folded in."""
+    if _down_on_kernel():
+        Kc = x.shape[1]
+        out = torch.zeros((x.shape[0], Rp), dtype=x.dtype, device=x.device)
+        ops.lora_down(x, p_kernel[:, :Kc], scale, out=out[:, :R])
+        return out
+    return ops.gemm(x, p_padded[:, :x.shape[1]])
+
+
+def lora_wgrad(up, x, scale, R, dtype):
+    """[R, K] = scale up[:, :R]^T x for up [M, Rp] with zero columns >= R."""
+    if _wgrad_on_kernel(x.shape[1], dtype, x.dtype):
+        return ops.lora_wgrad(up[:, :R], x, scale, dtype=dtype)
+    g = ops.gemm_layout(up, x, a_kmajor=True, b_kmajor=True)[:R]
+    return g * scale if scale != 1.0 else g.contiguous()                  # [R, K] is small; exact for a power of two
+
+
+def lora_mask_grads(g, state):
+    """Zero the gradient of the stacked B outside its diagonal blocks, in place: those entries are not parameters."""
+    if len(state.blocks) > 1:
+        keep = torch.zeros(g["B"].shape, dtype=torch.bool, device=g["B"].device)
+        for r0, r1, c0, c1 in state.blocks:
+            keep[r0:r1, c0:c1] = True
+        g["B"].masked_fill_(~keep, 0)
+    return g
+
+
+def lora_linear_forward(x, w, leaves, state, bias=None, res=None, out=None):
+    """y = x W^T (+ bias) (+ res) + s (x A^T) B^T by the rule above -> (y [M, N], up [M, Rp]: u = up[:, :R], columns >= R zero, kept
+    for the backward).  The base product is the call the Linear makes without an adapter."""
+    epi = (ops.EPI_BIAS_RES if bias is not None else ops.EPI_RES) if res is not None else (ops.EPI_BIAS if bias is not None else ops.EPI_NONE)
+    base = ops.gemm(x, w, bias=bias, res=res, epilogue=epi)
+    up = lora_down(x, leaves["A"], state.Ap, 1.0, state.R, state.Rp)
+    y = ops.gemm(up, state.sB, res=base, epilogue=ops.EPI_RES, out=out)
+    return y, up
+
+
+def _lora_weight_grads(x, up, dup, dy, state, dtype):
+    dA = lora_wgrad(dup, x, 1.0, state.R, dtype)                          # [R, K]
+    dBt = lora_wgrad(up, dy, state.s, state.R, dtype)                     # [R, N]
+    return lora_mask_grads({"A": dA, "B": dBt.t().contiguous()}, state)
+
+
+def lora_linear_backward(x, w, leaves, state, up, dy, res=None, need_dx=True, grad_dtype=None):
+    """Gradients of lora_linear_forward for dy [M, N] (up: what the forward returned): (dx [M, K] (+ res) or None,
+    {"A": dA [R, K], "B": dB [N, R]}) in grad_dtype (default: the operands' 16-bit dtype, as every other gradient of the step).  No dW.
+    Inside a step function dA / dB are produced on the side stream, as dW is (see _wgrad_overlap)."""
+    gd = grad_dtype or x.dtype
+    dup = lora_down(dy, state.Bt, state.sBtp, state.s, state.R, state.Rp)     # du = s dy B, [M, Rp]
+    side = _WGRAD["stream"] if x.is_cuda else None
+    if side is not None:
+        main = torch.cuda.current_stream(x.device)
+        side.wait_stream(main)                                        # x, u, du and dy are complete
+        with torch.cuda.stream(side):
+            g = _lora_weight_grads(x, up, dup, dy, state, gd)
+        for t in (x, up, dup, dy):
+            t.record_stream(side)
+        for t in g.values():
+            t.record_stream(main)
+    else:
+        g = _lora_weight_grads(x, up, dup, dy, state, gd)
+    dx = None
+    if need_dx:
+        dx_base, _, _ = linear_backward(x, w, dy, res=res, need_dw=False)
+        dx = ops.gemm(dup, state.At, res=dx_base, epilogue=ops.EPI_RES)
+    return dx, g
+
+
+class LoraConfig:
+    """The trainer's lora_* arguments (train_3d.py:168-173).  Dropout and adapter biases are not built: lora_dropout must be 0 and
+    bias "none" to train (the checkpoints' adapter_config default of 0.05 is accepted at merge time only, where dropout plays no part)."""
+
+    def __init__(self, r=64, lora_alpha=16, lora_dropout=0.0, bias="none"):
+        self.r, self.lora_alpha, self.lora_dropout, self.bias = int(r), float(lora_alpha), float(lora_dropout), bias
+
+    @property
+    def scaling(self):
+        return self.lora_alpha / self.r
+
+    def validate(self, for_merge=False):
+        if self.lora_dropout != 0.0 and not for_merge:
+            raise V3DError(f"lora_dropout={self.lora_dropout}: adapter dropout is not built, lora_dropout must be 0")
+        if self.bias != "none":
+            raise V3DError(f"lora_bias={self.bias!r}: adapter biases are not built, lora_bias must be 'none'")
+        if self.r % 16 or self.r < 16 or 3 * self.r > 384:
+            raise V3DError(f"lora_r={self.r} must be a multiple of 16 up to 128 (the stacked q|k|v rank 3 r is at most 384)")
+        return self
+
+
+def lora_merge_weight(w, leaves, state):
+    """W' = round(W + round(s B A)), B A accumulated in f32, on the device: one v3d_gemm with EPI_RES (A operand s B, W operand A^T,
+    the rank zero-padded to a multiple of 128), into a new tensor.  W [N, K] with K % 128 == 0."""
+    return ops.gemm(state.sB, state.At, res=w, epilogue=ops.EPI_RES)
+
+
+def lora_merge(w, a, b, s):
+    """lora_merge_weight for one adapter given as tensors (a [r, K], b [N, r], any r that is a multiple of 8): builds only the two
+    operands the merge reads - the inference loader's form."""
+    r, rp = a.shape[0], _pad(a.shape[0], 128)
+    sB = torch.zeros((b.shape[0], rp), dtype=w.dtype, device=w.device)
+    sB[:, :r] = (b.float() * float(s)).to(w.dtype)
+    return ops.gemm(sB, ops.transpose(a.contiguous(), out_cols=rp), res=w, epilogue=ops.EPI_RES)
+
+
+def lora_init(params, r=64, alpha=16, seed=0, qkv_rows=None):
+    """peft's LoraLayer.reset_lora_parameters on the seven decoder linears of every layer (find_all_linear_names: q_proj, k_proj, v_proj,
+    o_proj, gate_proj, up_proj, down_proj; not lm_head, tower, projector or grounding heads): A = kaiming_uniform_(a = sqrt 5) drawn
+    from torch's CPU generator (seeded; per module in the order above, layer by layer), B = 0.  Adds p["lora"] = {"qkv", "o",
+    "gate_up", "down"} (each {"A", "B"}, stacked for the fused rows; the trained leaves) and p["lora_state"] (LoraState per linear) to
+    each layer dict.  r % 16 == 0, and 3 r <= 384 for the stacked q|k|v."""
+    LoraConfig(r, alpha).validate()
+    gen = torch.Generator().manual_seed(seed)
+    s = float(alpha) / r
+    for p in params["layers"]:
+        hd_rows = {"qkv": None, "o": (p["o"].shape[0],), "gate_up": (p["gate_up"].shape[0] // 2,) * 2, "down": (p["down"].shape[0],)}
+        p["lora"], p["lora_state"] = {}, {}
+        for name in LORA_LINEARS:
+            w = p[name]
+            rows = hd_rows[name]
+            if rows is None:                                           # q | k | v: the split comes from the caller's layout
+                rows = qkv_rows or p.get("qkv_rows")            # (q rows, k rows, v rows) of the fused weight
+                if rows is None or sum(rows) != w.shape[0]:
+                    raise V3DError("lora_init: qkv_rows = (q rows, k rows, v rows) (or p['qkv_rows']) must split the fused q|k|v rows")
+            a_list, b_list = [], []
+            for n_rows in rows:
+                a = torch.empty((r, w.shape[1]), dtype=torch.float32)
+                torch.nn.init.kaiming_uniform_(a, a=math.sqrt(5), generator=gen)
+                a_list.append(a.to(w.dtype).to(w.device))
+                b_list.append(torch.zeros((n_rows, r), dtype=w.dtype, device=w.device))
+            A, B, blocks = lora_stack(a_list, b_list)
+            p["lora"][name] = {"A": A, "B": B}
+            p["lora_state"][name] = LoraState(p["lora"][name], s, blocks)
+    return params
+
+
+def lora_refresh(params):
+    """After an optimizer step: the derived copies of every adapter follow its leaves."""
+    for p in params["layers"]:
+        for name, st in p.get("lora_state", {}).items():
+            st.refresh(p["lora"][name])
+
+
+LORA_FROZEN = LORA_LINEARS                                                # with adapters, the base weights they sit on are frozen
+
+
+def trainable_tree(params, frozen=()):
+    """The sub-tree of params that is trained: everything except the leaves whose path has a component in `frozen` (names of this
+    tree: "qkv", "lm_head", "ln1", ... - LoRA adds LORA_FROZEN) and the adapters' derived state.  The tensors are shared with params,
+    so an optimizer built over this tree updates the model in place; the gradient tree of a step has exactly this structure."""
+    drop = set(frozen) | {"lora_state", "qkv_rows"}
+
+    def walk(t):
+        if isinstance(t, dict):
+            fz = drop | (set(LORA_FROZEN) if "lora" in t else set())
+            return {k: walk(v) for k, v in t.items() if k not in fz}
+        if isinstance(t, list):
+            return [walk(v) for v in t]
+        return t
+    return walk(params)
+
+
+def _drop_frozen(grads, frozen):
+    """The gradient tree without the entries whose key is in `frozen`, at every depth (trainable_tree's structure)."""
+    if not frozen:
+        return grads
+    if isinstance(grads, dict):
+        return {k: _drop_frozen(v, frozen) for k, v in grads.items() if k not in frozen}
+    if isinstance(grads, list):
+        return [_drop_frozen(v, frozen) for v in grads]
+    return grads
+
+
+def _towers_backward(dy, psaved, vsaved, params, frames, tokens, frozen):
+    """Backward of projector and tower from the projector rows' gradient -> (tower grads or None, projector grads or None).  A
+    sub-backward is skipped when nothing upstream of it is trainable: a frozen tower's backward is not run (the projector then forms no
+    dx), and with the projector frozen too neither is the projector's."""
+    pj = params["projector"]
+    tower = "vision" not in frozen
+    if not tower and "projector" in frozen:
+        return None, None
+    dfeat_in, pgrads = projector_backward(dy, psaved, pj["w1"], pj["w2"], need_dx=tower)
+    return (siglip_tower_backward(dfeat_in, vsaved, params["vision"], frames, tokens) if tower else None), pgrads
+
+
+def mlp_block_forward(h, ln_w, w_gate_up, w_down, eps=1e-6, lora=None):
     """The second half of Qwen2DecoderLayer.forward (modeling_qwen2.py:783-789): out = h + down(act(gate(n)) * up(n)), n = norm(h).
-    w_gate_up [2 I, H] = rows of gate_proj then rows of up_proj.  Returns (out, saved) - saved keeps what the backward re-reads."""
+    w_gate_up [2 I, H] = rows of gate_proj then rows of up_proj.  Returns (out, saved) - saved keeps what the backward re-reads.
+    lora = (leaves, states) of the layer: the two linears run by the LoRA rule and saved also keeps their u."""
     n = ops.rmsnorm(h, ln_w, eps)
+    if lora is not None:
+        gu, u_gu = lora_linear_forward(n, w_gate_up, lora[0]["gate_up"], lora[1]["gate_up"])
+        a = ops.swiglu(gu)
+        out, u_dn = lora_linear_forward(a, w_down, lora[0]["down"], lora[1]["down"], res=h)
+        return out, (h, n, gu, a, u_gu, u_dn)
     gu = ops.gemm(n, w_gate_up)                                       # [S, 2 I] planar
     a = ops.swiglu(gu)
     out = ops.gemm(a, w_down, res=h, epilogue=ops.EPI_RES)
     return out, (h, n, gu, a)
 
 
-def mlp_block_backward(dout, saved, ln_w, w_gate_up, w_down, eps=1e-6):
-    """Gradients of mlp_block_forward: (dh, {"ln": dln_w, "gate_up": dW [2 I, H], "down": dW [H, I]})."""
+def mlp_block_backward(dout, saved, ln_w, w_gate_up, w_down, eps=1e-6, lora=None):
+    """Gradients of mlp_block_forward: (dh, {"ln": dln_w, "gate_up": dW [2 I, H], "down": dW [H, I]}); with lora the two dW are
+    replaced by {"lora": {"gate_up": {"A", "B"}, "down": {"A", "B"}}}."""
+    if lora is not None:
+        h, n, gu, a, u_gu, u_dn = saved
+        da, g_dn = lora_linear_backward(a, w_down, lora[0]["down"], lora[1]["down"], u_dn, dout)
+        dgu = ops.swiglu_grad(gu, da)
+        dn, g_gu = lora_linear_backward(n, w_gate_up, lora[0]["gate_up"], lora[1]["gate_up"], u_gu, dgu)
+        dh, dln = ops.rmsnorm_grad(h, ln_w, dn, eps, add=dout)
+        return dh, {"ln": dln, "lora": {"gate_up": g_gu, "down": g_dn}}
     h, n, gu, a = saved
     da, dw_down, _ = linear_backward(a, w_down, dout)
     dgu = ops.swiglu_grad(gu, da)
@@ -217,32 +507,51 @@ class RopeTables:
         self.inv = ops.RopeTable(head_dim, n_pos, base, dtype, device, inv_freq=-ops.reference_inv_freq(head_dim, base))
 
 
-def attn_block_forward(h, ln_w, w_qkv, b_qkv, w_o, rope, n_q, n_kv, hd, eps=1e-6):
+def attn_block_forward(h, ln_w, w_qkv, b_qkv, w_o, rope, n_q, n_kv, hd, eps=1e-6, lora=None):
     """The first half of Qwen2DecoderLayer.forward (modeling_qwen2.py:771-781): out = h + o_proj(attention(rotary(qkv(norm(h))))).
-    w_qkv [(n_q + 2 n_kv) hd, H] = q_proj | k_proj | v_proj rows."""
+    w_qkv [(n_q + 2 n_kv) hd, H] = q_proj | k_proj | v_proj rows.  lora = (leaves, states) of the layer: qkv and o run by the LoRA rule."""
     S = h.shape[0]
     width = (n_q + 2 * n_kv) * hd
     n = ops.rmsnorm(h, ln_w, eps)
     qkv = torch.zeros((_pad(S, 128), width), dtype=h.dtype, device=h.device)      # rows >= S stay zero: the backward's key padding
-    ops.gemm(n, w_qkv, bias=b_qkv, epilogue=ops.EPI_BIAS, out=qkv[:S])
+    u_qkv = u_o = None
+    if lora is not None:
+        _, u_qkv = lora_linear_forward(n, w_qkv, lora[0]["qkv"], lora[1]["qkv"], bias=b_qkv, out=qkv[:S])
+    else:
+        ops.gemm(n, w_qkv, bias=b_qkv, epilogue=ops.EPI_BIAS, out=qkv[:S])
     ops.rope_apply(qkv[:S], n_q + n_kv, hd, rope.fwd)
     o = torch.empty((S, n_q * hd), dtype=h.dtype, device=h.device)
     lse = ops.attention_train(qkv, o, S, n_q, n_kv, 1.0 / math.sqrt(hd))
+    if lora is not None:
+        out, u_o = lora_linear_forward(o, w_o, lora[0]["o"], lora[1]["o"], res=h)
+        return out, (h, n, qkv, o, lse, u_qkv, u_o)
     out = ops.gemm(o, w_o, res=h, epilogue=ops.EPI_RES)
     return out, (h, n, qkv, o, lse)
 
 
-def attn_block_backward(dout, saved, ln_w, w_qkv, w_o, rope, n_q, n_kv, hd, eps=1e-6, materialised=False):
-    """Gradients of attn_block_forward: (dh, {"ln", "qkv", "qkv_bias", "o"})."""
-    h, n, qkv, o, lse = saved
+def attn_block_backward(dout, saved, ln_w, w_qkv, w_o, rope, n_q, n_kv, hd, eps=1e-6, materialised=False, lora=None):
+    """Gradients of attn_block_forward: (dh, {"ln", "qkv", "qkv_bias", "o"}); with lora (dh, {"ln", "qkv_bias", "lora": {"qkv", "o"}})."""
+    u_qkv = u_o = None
+    if lora is not None:
+        h, n, qkv, o, lse, u_qkv, u_o = saved
+    else:
+        h, n, qkv, o, lse = saved
     S = h.shape[0]
-    do, dw_o, _ = linear_backward(o, w_o, dout)
+    if lora is not None:
+        do, g_o = lora_linear_backward(o, w_o, lora[0]["o"], lora[1]["o"], u_o, dout)
+    else:
+        do, dw_o, _ = linear_backward(o, w_o, dout)
     dqkv = torch.empty((S, qkv.shape[1]), dtype=h.dtype, device=h.device)
     if materialised:
         attention_backward_materialised(qkv, do, dqkv, S, n_q, n_kv, hd, 1.0 / math.sqrt(hd))
     else:
         ops.attention_backward(qkv, o, do, lse, dqkv, S, n_q, n_kv, 1.0 / math.sqrt(hd))
     ops.rope_apply(dqkv, n_q + n_kv, hd, rope.inv)                                # the rotation's transpose
+    if lora is not None:
+        dn, g_qkv = lora_linear_backward(n, w_qkv, lora[0]["qkv"], lora[1]["qkv"], u_qkv, dqkv)
+        _, _, db_qkv = linear_backward(n, w_qkv, dqkv, need_dx=False, need_dw=False, need_db=True)
+        dh, dln = ops.rmsnorm_grad(h, ln_w, dn, eps, add=dout)
+        return dh, {"ln": dln, "qkv_bias": db_qkv, "lora": {"qkv": g_qkv, "o": g_o}}
     dn, dw_qkv, db_qkv = linear_backward(n, w_qkv, dqkv, need_db=True)
     dh, dln = ops.rmsnorm_grad(h, ln_w, dn, eps, add=dout)
     return dh, {"ln": dln, "qkv": dw_qkv, "qkv_bias": db_qkv, "o": dw_o}
@@ -251,13 +560,20 @@ def attn_block_backward(dout, saved, ln_w, w_qkv, w_o, rope, n_q, n_kv, hd, eps=
 def decoder_layer_forward(h, p, rope, n_q, n_kv, hd, eps=1e-6):
     """Qwen2DecoderLayer.forward (modeling_qwen2.py:727-801) for one sequence; p: dict of the layer's weights (ln1, qkv, qkv_bias, o,
     ln2, gate_up, down)."""
-    mid, s1 = attn_block_forward(h, p["ln1"], p["qkv"], p["qkv_bias"], p["o"], rope, n_q, n_kv, hd, eps)
-    out, s2 = mlp_block_forward(mid, p["ln2"], p["gate_up"], p["down"], eps)
+    lora = (p["lora"], p["lora_state"]) if "lora" in p else None
+    mid, s1 = attn_block_forward(h, p["ln1"], p["qkv"], p["qkv_bias"], p["o"], rope, n_q, n_kv, hd, eps, lora=lora)
+    out, s2 = mlp_block_forward(mid, p["ln2"], p["gate_up"], p["down"], eps, lora=lora)
     return out, (s1, s2)
 
 
 def decoder_layer_backward(dout, saved, p, rope, n_q, n_kv, hd, eps=1e-6, materialised=False):
     s1, s2 = saved
+    if "lora" in p:                                                   # the four base weights are frozen: no entry for them
+        lora = (p["lora"], p["lora_state"])
+        dmid, g2 = mlp_block_backward(dout, s2, p["ln2"], p["gate_up"], p["down"], eps, lora=lora)
+        dh, g1 = attn_block_backward(dmid, s1, p["ln1"], p["qkv"], p["o"], rope, n_q, n_kv, hd, eps, materialised, lora=lora)
+        return dh, {"ln1": g1["ln"], "qkv_bias": g1["qkv_bias"], "ln2": g2["ln"],
+                    "lora": {"qkv": g1["lora"]["qkv"], "o": g1["lora"]["o"], "gate_up": g2["lora"]["gate_up"], "down": g2["lora"]["down"]}}
     dmid, g2 = mlp_block_backward(dout, s2, p["ln2"], p["gate_up"], p["down"], eps)
     dh, g1 = attn_block_backward(dmid, s1, p["ln1"], p["qkv"], p["o"], rope, n_q, n_kv, hd, eps, materialised)
     return dh, {"ln1": g1["ln"], "qkv": g1["qkv"], "qkv_bias": g1["qkv_bias"], "o": g1["o"], "ln2": g2["ln"], "gate_up": g2["gate_up"],
@@ -267,24 +583,30 @@ def decoder_layer_backward(dout, saved, p, rope, n_q, n_kv, hd, eps=1e-6, materi
 # ------------------------------------------------------------------------------ the language model's step
 
 
-def llm_forward_backward(params, x, labels, rope, n_q, n_kv, hd, eps=1e-6, recompute=False):
+def llm_forward_backward(params, x, labels, rope, n_q, n_kv, hd, eps=1e-6, recompute=False, frozen=()):
     """Qwen2ForCausalLM.forward with labels (modeling_qwen2.py:1145-1217: decoder layers, final norm, LM head, shifted cross-entropy)
     and its backward for one sequence given as inputs_embeds x [S, H] (what prepare_inputs_labels_for_multimodal hands the LLM,
     llava_qwen.py:121-170).  params: {"layers": [layer dicts of decoder_layer_forward], "norm": [H], "lm_head": [V, H]}; labels [S]
     int64 on the device (-100 = ignored).  Returns (loss (f32 scalar tensor), dx [S, H], grads in params' structure).  All layers'
     activations are kept by default (about 1 GB per 7B layer at S = 6.8 k: 28 GB of the 288); recompute=True keeps only the layers'
     inputs and runs each layer's forward again in the backward, as the reference does under gradient checkpointing
-    (train_multi.sh:72) - same numbers, a third more work, 27 GB less."""
+    (train_multi.sh:72) - same numbers, a third more work, 27 GB less.
+    Layers that carry adapters (lora_init) run their four linears by the LoRA rule: the base weights get no dW and no gradient entry,
+    grads["layers"][i]["lora"] holds the adapters' {"A", "B"}.  frozen: further names of this tree ("lm_head", "norm", "ln1", "ln2",
+    "qkv_bias") whose leaves are not trained - no entry, and lm_head's dW product is not run.  The result has trainable_tree's structure."""
     with _wgrad_overlap(x.device):
         h, saved = llm_layers_forward(params, x, rope, n_q, n_kv, hd, eps, recompute)
         n = ops.rmsnorm(h, params["norm"], eps)
         logits = ops.gemm(n, params["lm_head"])
         loss, st = ops.cross_entropy(logits, labels)
         dlogits = ops.cross_entropy_grad(st)
-        dn, dw_head, _ = linear_backward(n, params["lm_head"], dlogits)
+        dn, dw_head, _ = linear_backward(n, params["lm_head"], dlogits, need_dw="lm_head" not in frozen)
         dh, dnorm = ops.rmsnorm_grad(h, params["norm"], dn, eps)
         dx, layer_grads = llm_layers_backward(dh, saved, params, rope, n_q, n_kv, hd, eps)
-        return loss, dx, {"layers": layer_grads, "norm": dnorm, "lm_head": dw_head}
+        # a frozen leaf has no gradient entry (trainable_tree's structure).  Only a frozen Linear saves work (lm_head's dW product is not
+        # run, as the adapted linears' are not): the norm weights' and qkv_bias's gradients fall out of kernels that also form dx (one
+        # fused v3d_rmsnorm_grad; a column sum of dqkv), so they are formed and dropped.
+        return loss, dx, _drop_frozen({"layers": layer_grads, "norm": dnorm, "lm_head": dw_head}, set(frozen))
 
 
 class _LayerInput:
@@ -647,7 +969,7 @@ def pe_mlp_backward(dpe, saved, p):
 
 
 def sample_forward_backward(params, patches, voxel_ids, pe_table, pre_ids, post_ids, labels, rope, frames, n_q, n_kv, hd, tokens=729, side=27, n=14,
-                            coord_rows=None, coord_pe=None, recompute=False, pe_mlp=None, pe_centres=None):
+                            coord_rows=None, coord_pe=None, recompute=False, pe_mlp=None, pe_centres=None, frozen=()):
     """One training sample end to end on the device (llava_qwen.py:121-205 -> llava_arch.py:336-836 -> modeling_qwen2.py:1145-1217):
     SigLIP tower -> mm_projector -> bilinear pool + 3-D PE + newline rows, spliced between the embedded text rows -> Qwen2 with labels;
     then the backward of all of it.  params: {"vision", "projector": {w1, b1, w2, b2}, "newline" [H], "embed" [vocab, H], "llm"};
@@ -659,7 +981,10 @@ def sample_forward_backward(params, patches, voxel_ids, pe_table, pre_ids, post_
     model dtype ([frames, n, n, 3]: the aggregated, with `discrete` voxelised, coordinates), pe_table and coord_pe are not read, and
     pe_centres [1, 3] is the (voxelised) box centre of the <coord> rows: tokens and centre are encoded as one batch, and the gradients of
     the token rows and of the summed <coord> rows go back through one backward into grads["pe_mlp"].
-    Returns (loss, grads in params' structure; "embed" is a dense [vocab, H] gradient with the text rows' sums)."""
+    Layers of params["llm"] that carry adapters (lora_init) run by the LoRA rule; frozen: names of this tree ("vision", "projector",
+    "embed", "lm_head", "norm", "ln1", ...) whose leaves are not trained - no gradient entry, a frozen tower's backward is not run.
+    Returns (loss, grads in trainable_tree(params, frozen)'s structure; "embed" is a dense [vocab, H] gradient with the text rows' sums)."""
+    frozen = set(frozen)
     if pe_mlp is not None and coord_rows is not None and coord_rows.numel() and (pe_centres is None or pe_centres.numel() != 3):
         raise V3DError("sample_forward_backward: pe_mlp with <coord> rows needs pe_centres [1, 3], the (voxelised) box centre")
     with _wgrad_overlap(patches.device):
@@ -674,7 +999,7 @@ def sample_forward_backward(params, patches, voxel_ids, pe_table, pre_ids, post_
             coord_pe = pe_c[0] if has_coord else None
         x, n_pre, n_vis = _build_inputs_embeds(params, y, voxel_ids, pe_table, pre_ids, post_ids, frames, tokens, side, n, coord_rows, coord_pe,
                                                pe_mlp, pe_rows)
-        loss, dx, llm_grads = llm_forward_backward(params["llm"], x, labels, rope, n_q, n_kv, hd, recompute=recompute)
+        loss, dx, llm_grads = llm_forward_backward(params["llm"], x, labels, rope, n_q, n_kv, hd, recompute=recompute, frozen=frozen)
         d_embed = torch.zeros_like(params["embed"])
         text_rows = torch.cat([torch.arange(n_pre, device=x.device), torch.arange(n_pre + n_vis, x.shape[0], device=x.device)])
         grads = {}
@@ -686,10 +1011,9 @@ def sample_forward_backward(params, patches, voxel_ids, pe_table, pre_ids, post_
             grads["pe_mlp"] = pe_mlp_backward(dpe, mlp_saved, pe_mlp)
         else:
             dfeat, d_newline = inputs_embeds_backward(dx, n_pre, frames, text_rows, torch.cat([pre_ids, post_ids]), d_embed, side=side, n=n)
-        dfeat_in, pgrads = projector_backward(dfeat.view(frames * tokens, H), psaved, pj["w1"], pj["w2"])
-        vgrads = siglip_tower_backward(dfeat_in, vsaved, params["vision"], frames, tokens)
+        vgrads, pgrads = _towers_backward(dfeat.view(frames * tokens, H), psaved, vsaved, params, frames, tokens, frozen)
         grads.update({"vision": vgrads, "projector": pgrads, "newline": d_newline, "embed": d_embed, "llm": llm_grads})
-        return loss, grads
+        return loss, _drop_frozen(grads, frozen)
 
 
 # ------------------------------------------------------------------------------ ZeRO-2 (scripts/zero2.json:22-34)
@@ -719,6 +1043,8 @@ class ZeroAdamW:
 
     def __init__(self, params, lr=1e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, bucket_elems=None, algorithm="ring",
                  lr_by_module=None, max_grad_norm=None, schedule=None):
+        if any("lora" in path.split(".") for path in _paths(params)):
+            raise V3DError("ZeroAdamW: lora adapters are not partitioned (ZeRO-2 over adapters is not built); use AdamW over trainable_tree(params)")
         import torch.distributed as dist
         from . import distributed as D
         self.D, self.dist = D, dist
@@ -931,7 +1257,7 @@ def _bce_head_forward_backward(head_type, gp, obj_feat, query_in, positive, pos_
 
 def ground_sample_forward_backward(params, patches, voxel_ids, pe_table, pre_ids, post_ids, ground_row, obj_mask, box_pe, positive, rope, frames,
                                    n_q, n_kv, hd, temperature=0.07, tokens=729, side=27, n=14, eps=1e-6, recompute=False, head_type="infonce",
-                                   pos_weight=None, pe_mlp=None, pe_centres=None):
+                                   pos_weight=None, pe_mlp=None, pe_centres=None, frozen=()):
     """A grounding sample of the joint training (llava_qwen.py:121-160 -> predict_box :239-310, object features llava_arch.py:351-376,
     479-501): the same tower -> projector -> splice -> decoder as sample_forward_backward, but the loss is the infonce loss between the
     <ground> token's final hidden state and the object proposals' features (masked means of the projector's patch rows + the box-centre
@@ -946,7 +1272,9 @@ def ground_sample_forward_backward(params, patches, voxel_ids, pe_table, pre_ids
     pe_mlp: the PositionEmbeddingMLP group of an `mlp` type; voxel_ids then holds the module's input in the model dtype, pe_table and
     box_pe are not read, and pe_centres [n_obj, 3] are the (voxelised) object centres: tokens and centres are encoded as one batch, and the
     gradient of obj = masked_mean + box_pe with respect to box_pe joins the token rows' in one backward into grads["pe_mlp"].
+    Adapters and frozen: as sample_forward_backward.
     Returns (loss, scores f32 [n_obj + 1] ('infonce') or [n_obj], grads) - grads["llm"] has no "lm_head" entry (the LM head takes no part)."""
+    frozen = set(frozen)
     if head_type not in GROUND_HEAD_TYPES:
         raise V3DError(f"ground_sample_forward_backward: head_type {head_type!r}, the reference has {GROUND_HEAD_TYPES}")
     if pe_mlp is not None and (pe_centres is None or pe_centres.numel() != 3 * obj_mask.shape[0]):
@@ -997,8 +1325,7 @@ def ground_sample_forward_backward(params, patches, voxel_ids, pe_table, pre_ids
             dfeat, d_newline = inputs_embeds_backward(dx, n_pre, frames, text_rows, torch.cat([pre_ids, post_ids]), d_embed, side=side, n=n)
         dy = dfeat.view(frames * tokens, H)
         ops.masked_mean_grad(obj_mask, d_obj_feat.contiguous(), dy, accumulate=True)      # the object features' share of the projector rows' gradient
-        dfeat_in, pgrads = projector_backward(dy, psaved, pj["w1"], pj["w2"])
-        vgrads = siglip_tower_backward(dfeat_in, vsaved, params["vision"], frames, tokens)
+        vgrads, pgrads = _towers_backward(dy, psaved, vsaved, params, frames, tokens, frozen)
         grads.update({"vision": vgrads, "projector": pgrads, "newline": d_newline, "embed": d_embed,
                       "llm": {"layers": layer_grads, "norm": d_norm}, "ground": g_ground})
-        return loss, scores, grads
+        return loss, scores, _drop_frozen(grads, frozen)

@@ -20,7 +20,12 @@ Position encodings: the shipped `avg-discrete-sin3d` (no parameters) and the lea
 `sample1[-discrete]-mlp`): the six tensors of `model.world_position_embedding.mlp.{0,1,3}` are parameters of the module (tree["pe_mlp"]) and
 take their `.grad` from LM and grounding samples alike.
 
-One sample per call, as the reference trains (`per_device_train_batch_size 1`, train_multi.sh:58).  Not here: DeepSpeed's engine, LoRA.
+One sample per call, as the reference trains (`per_device_train_batch_size 1`, train_multi.sh:58).  Not here: DeepSpeed's engine.
+
+LoRA (`lora_enable`, train_3d.py:168-173, 259-274): `LlavaQwenTrainable(tree, ..., lora=train.LoraConfig(r, lora_alpha), frozen=(...))` puts
+peft's init on the decoder's seven linears (`train.lora_init`); only the adapters and the leaves not named in `frozen` are `nn.Parameter`s
+(default with adapters: the projector and image_newline beside them), `loss.backward()` fills their `.grad` alone, a frozen tower's backward is not
+run, and `save_lora(dir)` writes the adapter directory the reference's trainer leaves (`loader.save_lora`; read back by `loader.load_lora`).
 """
 import torch
 import torch.nn as nn
@@ -31,6 +36,8 @@ from .engine import PE_MLP_KEYS, PE_MLP_PREFIX
 from .token_ids import IGNORE_INDEX, IMAGE_TOKEN_INDEX
 
 VIT = "model.vision_tower.vision_tower.vision_model."
+# with adapters, what is not trained unless the caller says otherwise: everything but the adapters, the projector and image_newline
+LORA_DEFAULT_FROZEN = ("vision", "embed", "lm_head", "norm", "ln1", "ln2", "qkv_bias", "ground", "pe_mlp")
 
 
 # head type -> its modules: (reference prefix, key in the tree's "ground", Sequential index of the LayerNorm); Linear at 0 and 3 throughout
@@ -74,7 +81,7 @@ class _SampleLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, module, args, *flat_params):
         args, kw = args
-        loss, grads = train.sample_forward_backward(module.param_tree(), *args, recompute=module.recompute, **kw)
+        loss, grads = train.sample_forward_backward(module.param_tree(), *args, recompute=module.recompute, frozen=module.frozen, **kw)
         ctx.grads = _match_grads(module, grads, ("ground.",) + module.unused_prefixes)      # the grounding head takes no part in an LM sample
         return loss.detach().clone()
 
@@ -111,7 +118,7 @@ class _GroundLoss(_SampleLoss):
     @staticmethod
     def forward(ctx, module, args, *flat_params):
         args, kw = args
-        loss, _, grads = train.ground_sample_forward_backward(module.param_tree(), *args, recompute=module.recompute, **kw)
+        loss, _, grads = train.ground_sample_forward_backward(module.param_tree(), *args, recompute=module.recompute, frozen=module.frozen, **kw)
         ctx.grads = _match_grads(module, grads, ("llm.lm_head",) + module.unused_prefixes)
         return loss.detach().clone()
 
@@ -133,15 +140,23 @@ def _training_position_type(wtype):
 class LlavaQwenTrainable(nn.Module):
     def __init__(self, tree, n_q, n_kv, head_dim=128, vit_heads=16, vit_inter=4304, rope_theta=1e6, max_pos=8192, recompute=False,
                  min_xyz=(-15, -15, -5), max_xyz=(15, 15, 5), voxel_size=0.1, ground_head_type=None, ground_temperature=0.07,
-                 ground_token_ids=None, world_position_embedding_type="avg-discrete-sin3d"):
+                 ground_token_ids=None, world_position_embedding_type="avg-discrete-sin3d", lora=None, frozen=None, lora_seed=0):
         """world_position_embedding_type: the checkpoint's config value; training runs the shipped 'avg-discrete-sin3d' and the `mlp` types
         (avg / sample1, with or without `discrete`; tree["pe_mlp"] = {w0, b0, ln_w, ln_b, w3, b3} is then required and trained); the other
         sin3d types are inference-only and are refused here, never trained as averages.  A "pe_mlp" group in the tree
         under the sin3d type is carried and gets no gradient.
         ground_head_type: None (no grounding head modelled) or 'infonce' / 'mlp' / 'score' with tree["ground"] in the layout of
         train.ground_sample_forward_backward; ground_temperature: the infonce head's config.ground_head_temperature; ground_token_ids:
-        config.ground_token_ids (the label ids whose row is the grounding query, llava_qwen.py:280)."""
+        config.ground_token_ids (the label ids whose row is the grounding query, llava_qwen.py:280).
+        lora: a train.LoraConfig - adapters on the decoder's seven linears (peft's init from torch's CPU generator seeded with lora_seed);
+        frozen: names of the tree whose leaves are not trained (train.trainable_tree; default with adapters LORA_DEFAULT_FROZEN: all but
+        the adapters, the projector and image_newline; without adapters nothing).  Frozen leaves are not nn.Parameters."""
         super().__init__()
+        self.lora = lora
+        self.frozen = tuple(frozen) if frozen is not None else (LORA_DEFAULT_FROZEN if lora is not None else ())
+        if lora is not None:
+            lora.validate()
+            train.lora_init(tree["llm"], r=lora.r, alpha=lora.lora_alpha, seed=lora_seed, qkv_rows=(n_q * head_dim, n_kv * head_dim, n_kv * head_dim))
         self.pe_kind, self.aggregation, self.discrete = _training_position_type(world_position_embedding_type)
         if self.pe_kind == "mlp" and "pe_mlp" not in tree:
             raise V3DError(f"world_position_embedding_type {world_position_embedding_type!r} but the tree has no 'pe_mlp' entry")
@@ -152,14 +167,15 @@ class LlavaQwenTrainable(nn.Module):
                 raise V3DError(f"ground_head_type {ground_head_type!r} but the tree has no 'ground' entry")
         self.ground_head_type, self.ground_temperature = ground_head_type, ground_temperature
         self.ground_token_ids = None if ground_token_ids is None else [int(i) for i in ground_token_ids]
-        flat = _flatten(tree)
+        self._full = tree if (lora is not None or self.frozen) else None      # every tensor, frozen ones and the adapters' state included
+        flat = _flatten(train.trainable_tree(tree, self.frozen) if self._full is not None else tree)
         self.names = [n for n, _ in flat]
         self._params = nn.ParameterList([nn.Parameter(t, requires_grad=True) for _, t in flat])
         self._shape = tree
         self.n_q, self.n_kv, self.hd, self.vit_heads, self.vit_inter = n_q, n_kv, head_dim, vit_heads, vit_inter
         self.recompute = recompute
         self.min_xyz, self.max_xyz, self.voxel_size = tuple(min_xyz), tuple(max_xyz), voxel_size
-        first = flat[0][1]
+        first = tree["newline"]
         self.rope = train.RopeTables(head_dim, max_pos, rope_theta, first.dtype, first.device)
         H = tree["newline"].shape[0]
         n_ids = int(round(max(b - a for a, b in zip(min_xyz, max_xyz)) / voxel_size)) + 1
@@ -167,7 +183,13 @@ class LlavaQwenTrainable(nn.Module):
 
     # ------------------------------------------------------------------ parameter tree <-> nn.Parameters
     def param_tree(self):
-        """The parameters as the dict / list tree `v3d.train` takes (the tensors ARE the nn.Parameters' storage)."""
+        """The parameters as the dict / list tree `v3d.train` takes (the tensors ARE the nn.Parameters' storage).  With adapters or
+        frozen leaves: the whole tree, whose trainable leaves are the nn.Parameters' storage; the adapters' derived copies are brought up
+        to date with their leaves (an optimizer may have stepped since)."""
+        if self._full is not None:
+            if self.lora is not None:
+                train.lora_refresh(self._full["llm"])
+            return self._full
         it = iter(self._params)
 
         def build(t):
@@ -306,6 +328,33 @@ class LlavaQwenTrainable(nn.Module):
         for k, v in getattr(self, "_passthrough", {}).items():      # unmodelled tensors of the source checkpoint, unchanged
             out[k] = v.clone()
         return out
+
+    def save_lora(self, lora_dir):
+        """The adapter directory of the reference's trainer (train_3d.py:1875-1884): adapter_config.json, adapter_model.bin (per-module
+        lora_A / lora_B under peft's keys, the stacked q|k|v and gate|up adapters taken apart exactly) and non_lora_trainables.bin (the
+        trained non-adapter tensors under peft's names of the reference's keys)."""
+        from . import loader
+        if self.lora is None:
+            raise V3DError("save_lora: this module was built without lora=")
+        adapters = {}
+        for i, L in enumerate(self._full["llm"]["layers"]):
+            for name, modules in train.LORA_MODULES.items():
+                a_list, b_list = train.lora_unstack(L["lora"][name]["A"], L["lora"][name]["B"], L["lora_state"][name].blocks)
+                for m, a, b in zip(modules, a_list, b_list):
+                    adapters[(i, m)] = (a, b)
+        base = ("self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.o_proj.weight",
+                "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
+        groups = {"vision": lambda k: k.startswith(VIT), "projector": lambda k: k.startswith("model.mm_projector."),
+                  "newline": lambda k: k == "model.image_newline", "embed": lambda k: k == "model.embed_tokens.weight",
+                  "lm_head": lambda k: k == "lm_head.weight", "norm": lambda k: k == "model.norm.weight",
+                  "ln1": lambda k: k.endswith("input_layernorm.weight"), "ln2": lambda k: k.endswith("post_attention_layernorm.weight"),
+                  "qkv_bias": lambda k: k.startswith("model.layers.") and k.endswith("_proj.bias"),
+                  "ground": lambda k: k.startswith("ground_head"), "pe_mlp": lambda k: k.startswith(PE_MLP_PREFIX)}
+        trained = [f for name, f in groups.items() if name not in self.frozen]
+        passthrough = set(getattr(self, "_passthrough", {}))
+        non_lora = {"base_model.model." + k: v for k, v in self.reference_state_dict().items()
+                    if k not in passthrough and not k.endswith(base) and any(f(k) for f in trained)}
+        loader.save_lora(lora_dir, adapters, non_lora, self.lora.r, self.lora.lora_alpha)
 
     # ------------------------------------------------------------------ forward (llava_qwen.py:121-205 for one video sample with labels)
     def forward(self, input_ids, labels, images, world_coords, coord_token_id=None, box_input=None):
