@@ -19,6 +19,7 @@ import torch
 
 from . import ops
 from ._native import V3DError
+from .linears import Linears
 
 
 def _up(x, m):
@@ -131,6 +132,12 @@ def random_state_dict(cfg: EngineConfig, dtype, device, seed=0, std=0.02, ground
             sd[pfx + "3.weight"], sd[pfx + "3.bias"] = rn(l.hidden, l.hidden), rn(l.hidden)
         sd["ground_head_zero_target"] = rn(l.hidden, s=1.0)
     return sd
+
+
+def _eos_ids(eos_token_id):
+    """eos_token_id (None, an int or a collection of ints) -> tuple of ints"""
+    ids = () if eos_token_id is None else (eos_token_id,) if isinstance(eos_token_id, int) else eos_token_id
+    return tuple(int(e) for e in ids)
 
 
 def _pad2(w, rows, cols):
@@ -264,6 +271,7 @@ class Engine:
 
     def _prep_llm(self, sd):
         l = self.cfg.llm
+        self.lin = Linears(self)           # everything behind it knows the weight format; nothing else does after construction
         self.l_layers = []
         for i in range(l.layers):
             p = f"model.layers.{i}."
@@ -278,19 +286,11 @@ class Engine:
                 wo=sd[p + "self_attn.o_proj.weight"].contiguous(),
                 wgu=ops.interleave_gate_up(sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"]),
                 wd=sd[p + "mlp.down_proj.weight"].contiguous()))
-            if self.llm_fp8:
-                L = self.l_layers[-1]
-                for k in ("wqkv", "wo", "wgu", "wd"):
-                    L[k + "8"] = ops.quantize_fp8_rows(L[k])
-            if self.llm_fp4:
-                L = self.l_layers[-1]
-                for k in ("wqkv", "wo", "wgu", "wd"):
-                    L[k + "4"] = ops.quantize_mxfp4_rows(L.pop(k))        # the 16-bit copy is dropped: nothing reads it again
+            self.lin.quantize_layer(self.l_layers[-1])
         self.l_nqkv = self.l_layers[0]["bqkv"].shape[0] if self.l_layers else 0
         self.l_norm = sd["model.norm.weight"].contiguous()
         self.l_head = _pad2(sd["lm_head.weight"], _up(l.vocab, 128), l.hidden)
-        if self.llm_fp8:
-            self.l_head8 = ops.quantize_fp8_rows(self.l_head)
+        self.lin.quantize_head()
 
     def grow_vocab(self, n):
         """resize_token_embeddings(n) with n > vocab (llava_qwen mirror): n - vocab rows equal to the mean of the existing rows are
@@ -303,8 +303,7 @@ class Engine:
         self.embed = torch.cat([emb, emb.float().mean(0, keepdim=True).to(emb.dtype).expand(add, -1)], 0).contiguous()
         head = self.l_head[: l.vocab]
         self.l_head = _pad2(torch.cat([head, head.float().mean(0, keepdim=True).to(head.dtype).expand(add, -1)], 0), _up(n, 128), l.hidden)
-        if self.llm_fp8:
-            self.l_head8 = ops.quantize_fp8_rows(self.l_head)
+        self.lin.quantize_head()
         l.vocab = n
         for k in ("_group_ctxs", "_group_rows", "_answer_st"):
             self.__dict__.pop(k, None)
@@ -535,48 +534,13 @@ class Engine:
         l = self.cfg.llm
         S = x.shape[0]
         hd, nh, nkv = self.hd, l.heads, l.kv_heads
-        h, qkv, att, act = self.l_h[:S], self.l_qkv[:S], self.l_att[:S], self.l_act[:S]
+        qkv, att, act = self.l_qkv[:S], self.l_att[:S], self.l_act[:S]
         kvw = nkv * hd
         scale = 1.0 / math.sqrt(hd)
-        fp8 = self.llm_quant and S > 8
-        if fp8:
-            s8 = self.l_s8[:S]
-            if self.llm_fp4:                         # MXFP4 weights against the same e4m3 activation rows (W4A8)
-                def qgemm(q8, L, key, out, **kw):
-                    return ops.gemm_mxfp4(q8, s8, *L[key + "4"], self.dtype, out=out, **kw)
-            else:
-                def qgemm(q8, L, key, out, **kw):
-                    qw, sw = L[key + "8"]
-                    return ops.gemm_fp8(q8, s8, qw, sw, self.dtype, out=out, **kw)
-
-            def lin(a, L, key, out, **kw):           # quantise the activation rows, then the e4m3 / MXFP4 GEMM
-                q8 = self.l_q8[:S, : a.shape[1]]
-                ops.quantize_fp8_rows(a, q8, s8)
-                return qgemm(q8, L, key, out, **kw)
-
-            def norm_lin(ln, L, key, out, **kw):     # RMSNorm + quantisation in one pass (the 16-bit rows are never stored)
-                q8 = self.l_q8[:S, : l.hidden]
-                ops.rmsnorm_quantize_fp8(x, ln, l.eps, q8, s8)
-                return qgemm(q8, L, key, out, **kw)
-        elif self.llm_fp4:                           # up to 8 rows: no 16-bit weights to fall back on - the W4A16 decode linears
-            dec_epi = {ops.EPI_BIAS: ops.DEC_BIAS, ops.EPI_RES: ops.DEC_RES, ops.EPI_SWIGLU: ops.DEC_SWIGLU}
-
-            def lin(a, L, key, out, epilogue=ops.EPI_NONE, **kw):
-                return self._dec_q(a, L, key, out, epilogue=dec_epi.get(epilogue, ops.DEC_NONE), **kw)
-
-            def norm_lin(ln, L, key, out, **kw):
-                ops.rmsnorm(x, ln, l.eps, out=h)
-                return lin(h, L, key, out, **kw)
-        else:
-            def lin(a, L, key, out, **kw):
-                return ops.gemm(a, L[key], out=out, **kw)
-
-            def norm_lin(ln, L, key, out, **kw):
-                ops.rmsnorm(x, ln, l.eps, out=h)
-                return ops.gemm(h, L[key], out=out, **kw)
+        lin = self.lin
         n_layers = len(self.l_layers)
         for i, L in enumerate(self.l_layers):
-            norm_lin(L["ln1"], L, "wqkv", qkv, bias=L["bqkv"], epilogue=ops.EPI_BIAS)
+            lin.prefill(x, L, "wqkv", qkv, ln=L["ln1"], bias=L["bqkv"], epilogue=ops.EPI_BIAS)
             if last_rows is not None and batch is None and i == n_layers - 1 and S > 1:
                 cache = self.kv[i]
                 ops.rope_kv_store(qkv, nh, nkv, hd, self.rope, cache, pos0=pos0)
@@ -596,9 +560,9 @@ class Engine:
                 else:
                     ops.attention(qkv, cache, cache[:, kvw:], att, B, Sq, pos0 + Sq, nh, nkv, hd, hd, qkv.stride(0), cache.stride(0),
                                   cache.stride(0), att.stride(0), Sq * qkv.stride(0), c3.stride(0), Sq * att.stride(0), hd, hd, hd, True, pos0, scale)
-                lin(att, L, "wo", x, res=x, epilogue=ops.EPI_RES)
-                norm_lin(L["ln2"], L, "wgu", act, epilogue=ops.EPI_SWIGLU)
-                lin(act, L, "wd", x, res=x, epilogue=ops.EPI_RES)
+                lin.prefill(att, L, "wo", x, res=x, epilogue=ops.EPI_RES)
+                lin.prefill(x, L, "wgu", act, ln=L["ln2"], epilogue=ops.EPI_SWIGLU)
+                lin.prefill(act, L, "wd", x, res=x, epilogue=ops.EPI_RES)
                 continue
             cache = self.kv[i]
             ops.rope_kv_store(qkv, nh, nkv, hd, self.rope, cache, pos0=pos0)       # K14 + cache append (rows pos0 .. pos0+S)
@@ -610,16 +574,10 @@ class Engine:
                 stamps["attn"](attn)      # bench: HIP events around one layer's launch
             else:
                 attn()
-            lin(att, L, "wo", x, res=x, epilogue=ops.EPI_RES)
-            if stamps is not None and i == 1 and not fp8 and "wgu" in L:      # bench: HIP events around the gate/up GEMM alone
-                ops.rmsnorm(x, L["ln2"], l.eps, out=h)
-                stamps["gemm"](lambda: ops.gemm(h, L["wgu"], epilogue=ops.EPI_SWIGLU, out=act))
-            elif stamps is not None and i == 1 and fp8:        # e4m3 / MXFP4: norm + quantisation pass, then the stamped GEMM
-                ops.rmsnorm_quantize_fp8(x, L["ln2"], l.eps, self.l_q8[:S, : l.hidden], s8)
-                stamps["gemm"](lambda: qgemm(self.l_q8[:S, : l.hidden], L, "wgu", act, epilogue=ops.EPI_SWIGLU))
-            else:
-                norm_lin(L["ln2"], L, "wgu", act, epilogue=ops.EPI_SWIGLU)
-            lin(act, L, "wd", x, res=x, epilogue=ops.EPI_RES)
+            lin.prefill(att, L, "wo", x, res=x, epilogue=ops.EPI_RES)
+            lin.prefill(x, L, "wgu", act, ln=L["ln2"], epilogue=ops.EPI_SWIGLU,      # bench: HIP events around layer 1's gate/up GEMM alone
+                        stamp=stamps["gemm"] if stamps is not None and i == 1 else None)
+            lin.prefill(act, L, "wd", x, res=x, epilogue=ops.EPI_RES)
         if batch is not None:
             return None
         self.kv_len = pos0 + S
@@ -633,49 +591,24 @@ class Engine:
         hd, nh, nkv = self.hd, l.heads, l.kv_heads
         kvw = nkv * hd
         scale = 1.0 / math.sqrt(hd)
-        att, act = self.ctx.d_att, self.ctx.d_act
+        att, act, h, lin = self.ctx.d_att, self.ctx.d_act[None], self.l_h[:1], self.lin
         for r in rows:
-            xr = x[r]
+            row = x[r: r + 1]
             ops.attention_decode(qkv[r], cache, cache[:, kvw:], att, pos0 + r + 1, nh, nkv, scale, self.dec_ws)
-            if self.llm_quant:
-                row = x[r: r + 1]
-                self._dec_q(att[None], L, "wo", row, res=row, epilogue=ops.DEC_RES)
-                h1 = ops.rmsnorm(row, L["ln2"], l.eps, out=self.l_h[:1])
-                self._dec_q(h1, L, "wgu", act[None], epilogue=ops.DEC_SWIGLU)
-                self._dec_q(act[None], L, "wd", row, res=row, epilogue=ops.DEC_RES)
-            else:
-                ops.linear_decode(att, L["wo"], xr, res=xr, epilogue=ops.DEC_RES)
-                ops.linear_decode(xr, L["wgu"], act, norm_weight=L["ln2"], eps=l.eps, epilogue=ops.DEC_SWIGLU)
-                ops.linear_decode(act, L["wd"], xr, res=xr, epilogue=ops.DEC_RES)
-
-    def _dec_q(self, a, L, key, out, **kw):
-        """decode linear of rows a over the quantised image of L[key]: e4m3 (llm_fp8, W8A16) or MXFP4 (llm_fp4, W4A16)"""
-        if self.llm_fp4:
-            q, e = L[key + "4"]
-            M = a.shape[0]
-            if M <= 4 or q.shape[1] % 128 == 0:      # K % 256 == 0: one launch (matrix-core form for 2..32 rows)
-                return ops.linear_decode_mxfp4_rows(a, q, e, out, **kw)
-            res = kw.pop("res", None)                # VALU form: 4 rows per launch; a row's bits do not depend on its group
-            for m in range(0, M, 4):
-                ops.linear_decode_mxfp4_rows(a[m: m + 4], q, e, out[m: m + 4], res=None if res is None else res[m: m + 4], **kw)
-            return out
-        return ops.linear_decode_fp8_rows(a, *L[key + "8"], out, **kw)
+            lin.rows(att[None], L, "wo", row, res=row, epilogue=ops.DEC_RES)
+            lin.norm_rows(row, L["ln2"], L, "wgu", act, h, fuse=True, epilogue=ops.DEC_SWIGLU)
+            lin.rows(act, L, "wd", row, res=row, epilogue=ops.DEC_RES)
 
     def _head(self, x_row):
-        """final RMSNorm + LM head on ONE row (K18: only the last position feeds generation)."""
-        l = self.cfg.llm
-        ops.rmsnorm(x_row, self.l_norm, l.eps, out=self.l_last[:1])
-        if self.llm_fp8:
-            ops.linear_decode_fp8_rows(self.l_last[:1], *self.l_head8, self.logits[:1])
-        else:
-            ops.linear_decode(self.l_last[0], self.l_head, self.logits[0])
-        return self.logits[0, : l.vocab]
+        """final RMSNorm + LM head on ONE row (K18: only the last position feeds generation); the norm is never fused here."""
+        self.lin.head(x_row, self.l_last[:1], self.logits[:1])
+        return self.logits[0, : self.cfg.llm.vocab]
 
     def decode_forward(self, x_row, pos):
         """One new token (x_row [1, hidden], in place) at position `pos`: 7 launches per layer, no host sync.
         RMSNorms are fused into the QKV / gate-up linears, rotary + cache append into one kernel."""
         l = self.cfg.llm
-        if self.llm_quant:                # e4m3 / MXFP4 weights: the row goes through the (unfused-norm) rows path as a group of one
+        if self.lin.fmt:                  # e4m3 / MXFP4 weights: the row goes through the (unfused-norm) rows path as a group of one
             g = getattr(self.ctx, "g1", None)
             if g is None:
                 g = self.ctx.g1 = self.new_group(1)
@@ -1032,15 +965,11 @@ class Engine:
         the one answer(..., stream=id) draws; with return_logits the result is (answers, logits [n_steps, G, V])."""
         sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, self._streams(streams, len(questions)), 1, return_logits)
         scene, st, x, P, lens, Sq, share = self._question_rows("answer_group", questions, max_new_tokens, box_inputs, coord_token_id)
-        G, l = len(questions), self.cfg.llm
+        G = len(questions)
         last = torch.tensor([g * Sq + lens[g] - 1 for g in range(G)], dtype=torch.int64, device=self.device)
         rows = st.rows
         ops.embed_gather(x, last, out=rows.x[:G])                                     # each question's last real row
-        ops.rmsnorm(rows.x[:G], self.l_norm, l.eps, out=rows.last[:G])
-        if self.llm_fp8:
-            ops.linear_decode_fp8_rows(rows.last[:G], *self.l_head8, rows.logits[:G])
-        else:
-            ops.linear_decode_rows(rows.last[:G], self.l_head, rows.logits[:G])
+        self.lin.head(rows.x[:G], rows.last[:G], rows.logits[:G])          # never fused: rows.last is written
         ctxs = st.ctxs[:G]
         for c, n in zip(ctxs, lens):
             c.kv_len = P + n
@@ -1148,39 +1077,22 @@ class Engine:
         scale = 1.0 / math.sqrt(hd)
         x, h, qkv, att, act = g.x[:M], g.h[:M], g.qkv[:M], g.att[:M], g.act[:M]
         sk = [p + 1 for p in positions]
-        if self.llm_quant:                # e4m3 (configs[3], W8A16) or MXFP4 (W4A16) weights, 16-bit activations: half / 0.27 of the bytes per step
-            def lin(a, L, key, out, **kw):
-                return self._dec_q(a, L, key, out, **kw)
-        else:
-            def lin(a, L, key, out, **kw):
-                return ops.linear_decode_rows(a, L[key], out, **kw)
-        # r04: with more than four rows the persistent decode linear forms the RMSNorm of its input rows itself (the bits of rmsnorm() +
-        # the unfused call: ops.linear_decode_rows_fuses_norm) - two launches fewer per layer and one before the LM head
-        def norm_lin(a, nw, w, out, quant=self.llm_quant, **kw):
-            if not quant and ops.linear_decode_rows_fuses_norm(M, w.shape[0], w.shape[1], kw.get("epilogue", ops.DEC_NONE)):
-                return ops.linear_decode_rows(a, w, out, norm_weight=nw, eps=l.eps, **kw)
-            return None
+        # r04: with more than four rows the persistent 16-bit decode linear forms the RMSNorm of its input rows itself (the bits of
+        # rmsnorm() + the unfused call: fuse=None, ops.linear_decode_rows_fuses_norm) - two launches fewer per layer and one before the LM
+        # head.  e4m3 (configs[3], W8A16) or MXFP4 (W4A16) weights, half / 0.27 of the bytes per step, never fuse it.
+        lin = self.lin
         for i, L in enumerate(self.l_layers):
             caches = [c.kv[i] for c in ctxs]
-            if norm_lin(x, L["ln1"], L.get("wqkv"), qkv, bias=L["bqkv"], epilogue=ops.DEC_BIAS) is None:
-                ops.rmsnorm(x, L["ln1"], l.eps, out=h)
-                lin(h, L, "wqkv", qkv, bias=L["bqkv"], epilogue=ops.DEC_BIAS)
+            lin.norm_rows(x, L["ln1"], L, "wqkv", qkv, h, fuse=None, bias=L["bqkv"], epilogue=ops.DEC_BIAS)
             ops.rope_kv_append_rows(qkv, nh, nkv, hd, self.rope, positions, [c[p] for c, p in zip(caches, positions)])
             ops.attention_decode_rows(qkv, caches, [c[:, kvw:] for c in caches], att, sk, nh, nkv, scale, g.ws, prefix=shared_prefix,
                                       prefix_kv=(prefix_kv[i], prefix_kv[i][:, kvw:]) if prefix_kv is not None and shared_prefix else None)
-            lin(att, L, "wo", x, res=x, epilogue=ops.DEC_RES)
-            if norm_lin(x, L["ln2"], L.get("wgu"), act, epilogue=ops.DEC_SWIGLU) is None:
-                ops.rmsnorm(x, L["ln2"], l.eps, out=h)
-                lin(h, L, "wgu", act, epilogue=ops.DEC_SWIGLU)
-            lin(act, L, "wd", x, res=x, epilogue=ops.DEC_RES)
+            lin.rows(att, L, "wo", x, res=x, epilogue=ops.DEC_RES)
+            lin.norm_rows(x, L["ln2"], L, "wgu", act, h, fuse=None, epilogue=ops.DEC_SWIGLU)
+            lin.rows(act, L, "wd", x, res=x, epilogue=ops.DEC_RES)
         for c, p in zip(ctxs, positions):
             c.kv_len = p + 1
-        if self.llm_fp8:
-            ops.rmsnorm(x, self.l_norm, l.eps, out=g.last[:M])
-            ops.linear_decode_fp8_rows(g.last[:M], *self.l_head8, g.logits[:M])
-        elif norm_lin(x, self.l_norm, self.l_head, g.logits[:M], quant=False) is None:     # (llm_fp4 keeps the 16-bit head)
-            ops.rmsnorm(x, self.l_norm, l.eps, out=g.last[:M])
-            ops.linear_decode_rows(g.last[:M], self.l_head, g.logits[:M])
+        lin.head(x, g.last[:M], g.logits[:M], fuse=None)
         return g.logits[:M, : l.vocab]
 
     def decode_group(self, g, ctxs, prompt_lens, max_new_tokens, logits_ready=False, shared_prefix=0, eos_token_id=None, lookahead=2, prefix_kv=None,
@@ -1211,7 +1123,7 @@ class Engine:
             for m, c in enumerate(ctxs):
                 ops.copy_rows(c.logits[:1], g.logits[m: m + 1])
         logits = g.logits[:M, : l.vocab]
-        eos = () if eos_token_id is None else ((int(eos_token_id),) if isinstance(eos_token_id, int) else tuple(int(e) for e in eos_token_id))
+        eos = _eos_ids(eos_token_id)
         if eos:
             st = self._eos_state(g, eos, max_new_tokens)
             st.done[:M].zero_()
@@ -1225,14 +1137,9 @@ class Engine:
                 ops.sample_rows(logits, toks[step], sampler.ws, sampler.T, sampler.top_k, sampler.top_p, sampler.seed, step, sampler.streams)
             if eos:
                 ops.eos_update(toks[step], st.eos, st.done[:M], st.n_done)
-                st.host[step].copy_(st.n_done, non_blocking=True)
-                st.events[step].record()
-                back = step - (lookahead - 1)
-                if back >= 0:
-                    st.events[back].synchronize()
-                    if int(st.host[back]) >= M:           # every row had finished by step `back`: the steps queued since are the overshoot
-                        n_steps = step + 1
-                        break
+                if self._late_word(st.host, st.events, st.n_done, step, lookahead) >= M:      # every row had finished by then: the steps
+                    n_steps = step + 1                                                       # queued since are the overshoot
+                    break
             if step + 1 == max_new_tokens:
                 break
             ops.embed_gather(self.embed, toks[step], out=g.x[:M])
@@ -1242,6 +1149,19 @@ class Engine:
             if own:
                 return toks[:n_steps].t(), sampler.logits
         return toks[:n_steps].t()
+
+    @staticmethod
+    def _late_word(host, events, word, step, lookahead):
+        """The host side of a stop test that never drains the launch queue: the device word of this step is copied into its pinned row
+        and an event recorded behind the copy; the host then waits for the event of step - (lookahead - 1) only and reads THAT step's
+        word (0 while no step is that old).  The buffers are the caller's, one row and one event per step."""
+        host[step].copy_(word, non_blocking=True)
+        events[step].record()
+        back = step - (lookahead - 1)
+        if back < 0:
+            return 0
+        events[back].synchronize()
+        return int(host[back])
 
     def _eos_state(self, g, eos, max_new_tokens):
         """Device / pinned buffers of the stop test, kept on the decode group."""
@@ -1259,7 +1179,7 @@ class Engine:
     @staticmethod
     def trim_at_eos(rows, eos_token_id):
         """rows [M, n] (host or device) -> list of 1-D host LongTensors, each cut after its first EOS id (generate's contract)."""
-        eos = () if eos_token_id is None else ((int(eos_token_id),) if isinstance(eos_token_id, int) else tuple(int(e) for e in eos_token_id))
+        eos = _eos_ids(eos_token_id)
         out = []
         for row in rows.cpu():
             if eos:
@@ -1282,7 +1202,7 @@ class Engine:
         keep = None
         if sampler is not None and sampler.return_logits:
             keep = torch.empty((max_new_tokens, 1, self.cfg.llm.vocab), dtype=self.dtype, device=self.device)
-        eos = () if eos_token_id is None else ((int(eos_token_id),) if isinstance(eos_token_id, int) else tuple(int(e) for e in eos_token_id))
+        eos = _eos_ids(eos_token_id)
         toks = torch.empty(max_new_tokens, dtype=torch.int64, device=self.device)
         st = None
         if eos and stopping is None:
@@ -1300,13 +1220,8 @@ class Engine:
             n = step + 1
             if st is not None:
                 ops.eos_update(toks[step: step + 1], st.eos, st.done[:1], st.n_done)
-                st.host[step].copy_(st.n_done, non_blocking=True)
-                st.events[step].record()
-                back = step - (lookahead - 1)
-                if back >= 0:
-                    st.events[back].synchronize()
-                    if int(st.host[back]) >= 1:
-                        break
+                if self._late_word(st.host, st.events, st.n_done, step, lookahead) >= 1:
+                    break
             elif eos and int(toks[step]) in eos:
                 break
             if stopping is not None and stopping(toks[:n]):
@@ -1339,7 +1254,7 @@ class Engine:
         allocated inside the loop."""
         l = self.cfg.llm
         B = int(num_beams)
-        eos = () if eos_token_id is None else ((int(eos_token_id),) if isinstance(eos_token_id, int) else tuple(int(e) for e in eos_token_id))
+        eos = _eos_ids(eos_token_id)
         K = max(2, 1 + len(eos)) * B
         if not 1 <= B <= ops.BEAM_MAX_B or K > ops.BEAM_MAX_K:
             raise V3DError(f"beam search takes 1 to {ops.BEAM_MAX_B} beams and at most {ops.BEAM_MAX_K} candidates per step "
@@ -1375,14 +1290,9 @@ class Engine:
         for t in range(max_new_tokens):
             ops.beam_topk(x, bs.running, K, bs.cand_score, bs.cand_flat, bs.topk_ws, done=bs.done, V=l.vocab)
             ops.beam_step(bs, t)
-            st.beam_host[t].copy_(bs.done, non_blocking=True)
-            st.beam_events[t].record()
-            back = t - (lookahead - 1)
-            if back >= 0:
-                st.beam_events[back].synchronize()
-                if int(st.beam_host[back]):                     # the search ended at step `back`: what was queued since changed nothing
-                    n_steps = t + 1
-                    break
+            if self._late_word(st.beam_host, st.beam_events, bs.done, t, lookahead):      # the search had ended by then: what was queued
+                n_steps = t + 1                                                          # since changed nothing
+                break
             if t + 1 == max_new_tokens:
                 break
             cur = (t & 1) * half
