@@ -521,6 +521,24 @@ int v3d_sample_rows_host(const float* logits, int64_t ldx, int M, int V, float t
 /* Philox4x32-10 as the sampler uses it (counter[4], key[2] -> out[4]): the known-answer hook of the tests. */
 int v3d_philox4x32_10_host(const uint32_t* counter, const uint32_t* key, uint32_t* out);
 
+/* ------------------------------------------------------------------ logits processors - */
+/* Added under ABI 7 (no entry changed).  The rule is DESIGN section 2, "Logits processors, stated once": transformers'
+ * RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor and MinNewTokensLengthLogitsProcessor over the tokens generated so
+ * far, in that order, applied in place to the 16-bit logits the token choice reads next.
+ *
+ * v3d_logits_process_rows: M <= 32 rows x + m * ldx of V columns; columns [V, ldx) are never written.  history: device int64, row
+ * m's j-th generated token at history[j * ld_step + m] (ld_step >= M), n_prev <= 8192 of them (the step number).  penalty > 0 (1:
+ * off): every distinct history id v gets x[v] = round16(x[v] < 0 ? x[v] * penalty : x[v] / penalty), from the unpenalised value,
+ * once.  ngram >= 0 (0: off): when n_prev + 1 >= ngram every id that would complete an n-gram already in the history is set to
+ * -inf.  min_new >= 0 (0: off): while n_prev < min_new the n_eos ids of eos_ids (device int64) are set to -inf.  Ids outside [0, V)
+ * are skipped.  One launch, one workgroup per row, work proportional to n_prev; no launch when nothing applies at this step.
+ * v3d_logits_process_rows_host: the same arithmetic (csrc/logits_rule.h) over f32 logits in host memory that hold values of
+ * `dtype` (V3D_F16 / V3D_BF16). */
+int v3d_logits_process_rows(void* logits, int64_t ldx, int M, int V, int dtype, const int64_t* history, int64_t ld_step, int n_prev,
+                            float penalty, int ngram, int min_new, const int64_t* eos_ids, int n_eos, void* stream);
+int v3d_logits_process_rows_host(float* logits, int64_t ldx, int M, int V, int dtype, const int64_t* history, int64_t ld_step, int n_prev,
+                                 float penalty, int ngram, int min_new, const int64_t* eos_ids, int n_eos);
+
 /* ------------------------------------------------------------------ grounding (K19, K20) - */
 
 /* K19  llava_arch.py:357-372, object_feature_type 'patch14': mask[o, f, py, px] = 1 iff at least `thresh`

@@ -1,5 +1,5 @@
 // Host side of the C ABI: error reporting and the host-only helpers (frame sampling,
-// greedy max-coverage frame selection, the beam-search step's twin, the sampler's twin).
+// greedy max-coverage frame selection, the beam-search step's twin, the sampler's twin, the logits processors' twin).
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -11,6 +11,7 @@
 #include "v3d.h"
 #include "beam_step.h"
 #include "sample_rule.h"
+#include "logits_rule.h"
 
 namespace v3d {
 
@@ -191,6 +192,56 @@ extern "C" int v3d_sample_rows_host(const float* logits, int64_t ldx, int M, int
     }
     out_index[m] = best_i;
     if (kept) kept[m] = n;
+  }
+  return V3D_OK;
+}
+
+// The twin of v3d_logits_process_rows over f32 logits that hold 16-bit values ("Logits processors, stated once"):
+// the kernel's arithmetic (logits_rule.h) in the kernel's order - every gather of the penalty before any of its stores, then the
+// n-gram bans, then the EOS bans.
+extern "C" int v3d_logits_process_rows_host(float* logits, int64_t ldx, int M, int V, int dtype, const int64_t* history, int64_t ld_step, int n_prev,
+                                            float penalty, int ngram, int min_new, const int64_t* eos_ids, int n_eos) {
+  if (!logits || (!history && n_prev > 0) || (!eos_ids && n_eos > 0)) {
+    v3d::set_error("v3d_logits_process_rows_host: null pointer");
+    return V3D_E_INVALID;
+  }
+  if (n_prev > v3d::LOGITS_MAX_HISTORY) {
+    v3d::set_error("v3d_logits_process_rows_host: a history of %d tokens exceeds LOGITS_MAX_HISTORY = %d", n_prev, v3d::LOGITS_MAX_HISTORY);
+    return V3D_E_INVALID;
+  }
+  if (!v3d::logits_args_ok(M, V, ld_step, n_prev, penalty, ngram, min_new, n_eos) || (dtype != V3D_F16 && dtype != V3D_BF16) || (M > 1 && ldx < V)) {
+    v3d::set_error("v3d_logits_process_rows_host: bad arguments (M=%d V=%d ldx=%lld dtype=%d ld_step=%lld n_prev=%d penalty=%g ngram=%d min_new=%d n_eos=%d)", M, V,
+                   (long long)ldx, dtype, (long long)ld_step, n_prev, (double)penalty, ngram, min_new, n_eos);
+    return V3D_E_INVALID;
+  }
+  const bool bf = dtype == V3D_BF16;
+  const int L = n_prev;
+  const float ninf = v3d::logits_widen(v3d::logits_neg_inf(bf), bf);
+  std::vector<uint16_t> staged((size_t)L);
+  for (int m = 0; m < M; ++m) {
+    float* row = logits + (int64_t)m * ldx;
+    const int64_t* h = history + m;
+    if (penalty != 1.f) {
+      for (int j = 0; j < L; ++j) {
+        const int64_t v = h[(int64_t)j * ld_step];
+        if (v3d::logits_id_ok(v, V)) staged[(size_t)j] = v3d::logits_penalised(v3d::logits_round16(row[v], bf), penalty, bf);
+      }
+      for (int j = 0; j < L; ++j) {
+        const int64_t v = h[(int64_t)j * ld_step];
+        if (v3d::logits_id_ok(v, V)) row[v] = v3d::logits_widen(staged[(size_t)j], bf);
+      }
+    }
+    if (ngram > 0 && L + 1 >= ngram) {
+      for (int i = 0; i <= L - ngram; ++i) {
+        if (!v3d::logits_ngram_match(h, ld_step, L, ngram, i)) continue;
+        const int64_t v = h[(int64_t)(i + ngram - 1) * ld_step];
+        if (v3d::logits_id_ok(v, V)) row[v] = ninf;
+      }
+    }
+    if (L < min_new) {
+      for (int e = 0; e < n_eos; ++e)
+        if (v3d::logits_id_ok(eos_ids[e], V)) row[eos_ids[e]] = ninf;
+    }
   }
   return V3D_OK;
 }

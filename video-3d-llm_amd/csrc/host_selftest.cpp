@@ -2,6 +2,7 @@
 // g++ -fsanitize=address,undefined (GPU AddressSanitizer is not available on this pool; the device entry points validate their
 // arguments on the host before any launch and are exercised by tests/test_abi_host.py and the -m gpu tests).
 // Exercises the valid paths on ragged sizes and every argument-validation branch; exits non-zero on a wrong answer.
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -156,6 +157,62 @@ int main() {
     CHECK(v3d_sample_rows_host(x.data(), ldx, 33, V, 1.f, 0, 1.f, 0, 0, nullptr, tok.data(), nullptr) == V3D_E_INVALID);
     CHECK(v3d_sample_rows_host(x.data(), V - 1, M, V, 1.f, 0, 1.f, 0, 0, nullptr, tok.data(), nullptr) == V3D_E_INVALID);
     CHECK(v3d_sample_rows_host(nullptr, ldx, M, V, 1.f, 0, 1.f, 0, 0, nullptr, tok.data(), nullptr) == V3D_E_INVALID);
+  }
+  // logits processors: the twin on scripted histories (V = 12 of ld 16, two rows at a step stride of 3), every control alone and together, both
+  // 16-bit formats, the pad columns, out-of-range ids, and the argument check
+  {
+    const int M = 2, V = 12, ldx = 16, ld = 3, L = 7;
+    //                      row 0: 1 2 3 1 2 9 1   (bigram "1 2" seen twice, unigram 1 three times);  row 1: 5 5 5 77 -4 5 5 (out-of-range ids)
+    const int64_t hist[L * ld] = {1, 5, -1, 2, 5, -1, 3, 5, -1, 1, 77, -1, 2, -4, -1, 9, 5, -1, 1, 5, -1};
+    const int64_t eos[3] = {0, 11, 400};
+    const float ninf = -HUGE_VALF;
+    for (int dtype : {V3D_F16, V3D_BF16}) {
+      std::vector<float> x0((size_t)M * ldx);
+      for (int i = 0; i < M * ldx; ++i) x0[i] = (float)(i % 7) * 0.5f - 1.5f;          // exact in both formats; negatives, zeros, positives
+      auto run = [&](std::vector<float>& x, int n_prev, float p, int n, int k, int n_eos) {
+        return v3d_logits_process_rows_host(x.data(), ldx, M, V, dtype, hist, ld, n_prev, p, n, k, eos, n_eos);
+      };
+      std::vector<float> x = x0;
+      CHECK(run(x, L, 1.f, 0, 0, 3) == V3D_OK && x == x0);                             // all off: nothing moves
+      CHECK(run(x, L, 2.f, 0, 0, 0) == V3D_OK);                                        // penalty 2 (exact): once per distinct id
+      for (int m = 0; m < M; ++m)
+        for (int v = 0; v < ldx; ++v) {
+          const bool seen = m == 0 ? (v == 1 || v == 2 || v == 3 || v == 9) : v == 5;
+          const float a = x0[(size_t)m * ldx + v];
+          CHECK(x[(size_t)m * ldx + v] == (seen ? (a < 0.f ? a * 2.f : a / 2.f) : a));
+        }
+      x = x0;
+      CHECK(run(x, L, 1.f, 2, 0, 0) == V3D_OK);                                        // bigrams: row 0 ends in 1 -> 2 banned; row 1 ends in 5 -> 5 and 77 (skipped)
+      for (int m = 0; m < M; ++m)
+        for (int v = 0; v < ldx; ++v) CHECK(x[(size_t)m * ldx + v] == ((m == 0 && v == 2) || (m == 1 && v == 5) ? ninf : x0[(size_t)m * ldx + v]));
+      x = x0;
+      CHECK(run(x, L, 1.f, 3, 0, 0) == V3D_OK);                                        // trigrams: row 0 ends in "9 1" (new) -> none; row 1 ends in "5 5" -> 5
+      for (int m = 0; m < M; ++m)
+        for (int v = 0; v < ldx; ++v) CHECK(x[(size_t)m * ldx + v] == ((m == 1 && v == 5) ? ninf : x0[(size_t)m * ldx + v]));
+      x = x0;
+      CHECK(run(x, 1, 1.f, 3, 0, 0) == V3D_OK && x == x0);                             // L + 1 < n
+      CHECK(run(x, L, 1.f, 0, L + 1, 3) == V3D_OK);                                    // L < k: EOS ids 0 and 11 (400 is out of range)
+      for (int m = 0; m < M; ++m)
+        for (int v = 0; v < ldx; ++v) CHECK(x[(size_t)m * ldx + v] == (v == 0 || v == 11 ? ninf : x0[(size_t)m * ldx + v]));
+      x = x0;
+      CHECK(run(x, L, 1.f, 0, L, 3) == V3D_OK && x == x0);                             // L == k: off
+      CHECK(run(x, L, 1.3f, 1, L + 1, 3) == V3D_OK);                                   // all three: the bans win over the penalty
+      CHECK(x[1] == ninf && x[2] == ninf && x[3] == ninf && x[9] == ninf && x[0] == ninf && x[11] == ninf && x[4] == x0[4] && x[12] == x0[12]);
+      CHECK(x[ldx + 5] == ninf && x[ldx + 0] == ninf && x[ldx + 6] == x0[ldx + 6] && x[ldx + 13] == x0[ldx + 13]);
+      x = x0;
+      CHECK(run(x, 0, 1.3f, 2, 0, 0) == V3D_OK && x == x0);                            // an empty history
+      CHECK(v3d_logits_process_rows_host(x.data(), ldx, M, V, dtype, nullptr, ld, 0, 1.3f, 2, 0, nullptr, 0) == V3D_OK && x == x0);
+      CHECK(run(x, L, 0.f, 0, 0, 0) == V3D_E_INVALID && run(x, L, -1.f, 0, 0, 0) == V3D_E_INVALID && run(x, L, 1.f, -1, 0, 0) == V3D_E_INVALID);
+      CHECK(run(x, L, 1.f, 0, -1, 0) == V3D_E_INVALID && run(x, -1, 1.f, 0, 0, 0) == V3D_E_INVALID && run(x, 8193, 1.f, 0, 0, 0) == V3D_E_INVALID);
+      CHECK(std::strstr(v3d_last_error(), "LOGITS_MAX_HISTORY") != nullptr);
+      CHECK(v3d_logits_process_rows_host(x.data(), ldx, 33, V, dtype, hist, 33, L, 1.f, 0, 0, eos, 3) == V3D_E_INVALID);
+      CHECK(v3d_logits_process_rows_host(x.data(), V - 1, M, V, dtype, hist, ld, L, 1.f, 0, 0, eos, 3) == V3D_E_INVALID);
+      CHECK(v3d_logits_process_rows_host(x.data(), ldx, M, V, dtype, hist, 1, L, 1.f, 0, 0, eos, 3) == V3D_E_INVALID);       // ld_step < M
+      CHECK(v3d_logits_process_rows_host(x.data(), ldx, M, V, V3D_F32, hist, ld, L, 1.f, 0, 0, eos, 3) == V3D_E_INVALID);
+      CHECK(v3d_logits_process_rows_host(nullptr, ldx, M, V, dtype, hist, ld, L, 1.f, 0, 0, eos, 3) == V3D_E_INVALID);
+      CHECK(v3d_logits_process_rows_host(x.data(), ldx, M, V, dtype, nullptr, ld, L, 1.f, 0, 0, eos, 3) == V3D_E_INVALID);
+      CHECK(v3d_logits_process_rows_host(x.data(), ldx, M, V, dtype, hist, ld, L, 1.f, 0, 1, nullptr, 3) == V3D_E_INVALID);
+    }
   }
   std::puts("host_selftest ok");
   return 0;

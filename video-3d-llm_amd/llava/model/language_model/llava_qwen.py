@@ -17,7 +17,9 @@ v3d.engine.Engine's HBM layouts.  Call contracts mirrored (3-D eval drivers):
 generate is greedy only, no autograd (the loss is a forward value); sampling / beams / box_labels raise NotImplementedError there, unknown keyword
 arguments raise TypeError - nothing is silently dropped.  Sampling has its own entry, model.generate_sample(..., temperature=T, top_p=p,
 top_k=k, seed=s) (the device sampler, seeded).  Beam search has its own entry, model.generate_beam(..., num_beams=N, length_penalty=p):
-generate's arguments and return.
+generate's arguments and return.  The logits processors (repetition_penalty, no_repeat_ngram_size, min_new_tokens; DESIGN section 2, "Logits
+processors, stated once") are read from model.generation_config, where transformers keeps them, or given outright as processors=dict(...):
+generate and generate_sample honour them; generate_beam never reads generation_config's and refuses those given outright.
 """
 import json
 import os
@@ -62,6 +64,7 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
     config_class = LlavaQwenConfig
     _GENERATE_KW = {"max_new_tokens", "do_sample", "num_beams", "temperature", "top_p", "top_k", "use_cache", "attention_mask",
                     "position_ids", "stopping_criteria", "eos_token_id", "pad_token_id", "video_dict", "max_length"}
+    _PROCESSOR_KW = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens")        # read from generation_config (_processors)
 
     def __init__(self, config, state_dict=None, dtype=torch.float16, device=None, llm_fp8=False, max_frames=32, llm_fp4=False):
         super().__init__()
@@ -171,6 +174,26 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
                                                    else getattr(self.config, "eos_token_id", None))
         return e
 
+    def _unknown(self, what, kwargs):
+        unknown = set(kwargs) - self._GENERATE_KW
+        if unknown:
+            hint = ""
+            if unknown & set(self._PROCESSOR_KW):
+                hint = (f"; {sorted(unknown & set(self._PROCESSOR_KW))} are read from model.generation_config "
+                        "(e.g. model.generation_config.no_repeat_ngram_size = 3), not from keywords")
+            raise TypeError(f"LlavaQwenForCausalLM.{what}: unsupported arguments {sorted(unknown)} (accepted: {sorted(self._GENERATE_KW)}){hint}")
+
+    def _processors(self):
+        """The logits processors of generation_config (the checkpoint's generation_config.json, or what the caller has set on
+        model.generation_config), as Engine.generate's keywords; a missing or None entry is off (1.0 / 0 / 0), as in transformers."""
+        gc = getattr(self, "generation_config", None)
+        out = {}
+        for name, off, cast in (("repetition_penalty", 1.0, float), ("no_repeat_ngram_size", 0, int), ("min_new_tokens", 0, int)):
+            v = getattr(gc, name, None)
+            if v is not None and v != off:
+                out[name] = cast(v)
+        return out
+
     def _sample(self, input_ids, images, video_dict):
         if input_ids is None or input_ids.shape[0] != 1:
             raise NotImplementedError("batch size 1, as every 3-D eval driver uses")
@@ -229,41 +252,40 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
 
     # ------------------------------------------------------------------ generate (llava_qwen.py:208-226)
     @torch.no_grad()
-    def generate(self, inputs=None, images=None, image_sizes=None, modalities=("image",), **kwargs):
-        unknown = set(kwargs) - self._GENERATE_KW
-        if unknown:
-            raise TypeError(f"LlavaQwenForCausalLM.generate: unsupported arguments {sorted(unknown)} (accepted: {sorted(self._GENERATE_KW)})")
+    def generate(self, inputs=None, images=None, image_sizes=None, modalities=("image",), processors=None, **kwargs):
+        """processors: dict(repetition_penalty, no_repeat_ngram_size, min_new_tokens) - the logits processors given outright (a missing entry
+        is off); None (default): those of model.generation_config."""
+        self._unknown("generate", kwargs)
         if kwargs.get("do_sample") or (kwargs.get("num_beams") or 1) != 1:
             raise NotImplementedError("greedy decoding only (the 3-D eval drivers run temperature 0, num_beams 1); beam search is "
                                       "generate_beam(input_ids, images=..., video_dict=..., num_beams=N), sampling is "
                                       "generate_sample(input_ids, images=..., video_dict=..., temperature=T, top_p=p, top_k=k, seed=s)")
-        return self._generate(inputs, images, kwargs)
+        return self._generate(inputs, images, kwargs, processors=processors)
 
     @torch.no_grad()
-    def generate_beam(self, inputs=None, images=None, image_sizes=None, modalities=("image",), num_beams=1, length_penalty=1.0, **kwargs):
+    def generate_beam(self, inputs=None, images=None, image_sizes=None, modalities=("image",), num_beams=1, length_penalty=1.0, processors=None, **kwargs):
         """generate(...) with num_beams beams (Engine.beam_search: transformers' beam search for do_sample=False, early_stopping=False,
-        num_return_sequences=1): the same arguments, the same [1, n_new] return.  num_beams=1 is generate()."""
-        unknown = set(kwargs) - self._GENERATE_KW
-        if unknown:
-            raise TypeError(f"LlavaQwenForCausalLM.generate_beam: unsupported arguments {sorted(unknown)} (accepted: {sorted(self._GENERATE_KW)})")
+        num_return_sequences=1): the same arguments, the same [1, n_new] return.  num_beams=1 is generate().
+        With num_beams > 1 the logits processors of generation_config are NOT read (a checkpoint that ships a repetition_penalty searches
+        as it always has); processors given outright (processors=dict(...) with a control on) are refused: not built under beams."""
+        self._unknown("generate_beam", kwargs)
         if kwargs.get("do_sample"):
             raise NotImplementedError("beam search here is deterministic (do_sample=False)")
         if int(num_beams) > 1 and kwargs.get("stopping_criteria"):
             raise NotImplementedError("stopping_criteria cannot be combined with beams: they stop by EOS ids and max_new_tokens only")
-        return self._generate(inputs, images, kwargs, num_beams=int(num_beams), length_penalty=float(length_penalty))
+        return self._generate(inputs, images, kwargs, num_beams=int(num_beams), length_penalty=float(length_penalty), processors=processors)
 
     @torch.no_grad()
     def generate_sample(self, inputs=None, images=None, image_sizes=None, modalities=("image",), temperature=None, top_p=None, top_k=None, seed=None,
-                        stream=0, **kwargs):
+                        stream=0, processors=None, **kwargs):
         """generate(...) with do_sample=True (Engine's sampler: transformers' temperature, top-k and top-p warpers and one seeded draw per
         token on the device; DESIGN section 2, "Sampling, stated once"): the same arguments, the same [1, n_new] return.  temperature /
         top_k / top_p left as None fall back to self.generation_config, as transformers does (a missing or None entry: 1.0 / 0 / 1.0).
         seed=None draws one 63-bit seed from torch's default CPU generator, so torch.manual_seed makes a run reproducible; the random
         stream itself is the project's own (Philox4x32-10), not torch's.  stream: the id of this prompt's random stream under the seed (the eval
-        runners pass the question's index, so a record does not depend on how questions are batched)."""
-        unknown = set(kwargs) - self._GENERATE_KW
-        if unknown:
-            raise TypeError(f"LlavaQwenForCausalLM.generate_sample: unsupported arguments {sorted(unknown)} (accepted: {sorted(self._GENERATE_KW)})")
+        runners pass the question's index, so a record does not depend on how questions are batched).  processors: as generate - the logits
+        processors run before the sampling warpers, as in transformers."""
+        self._unknown("generate_sample", kwargs)
         if kwargs.get("do_sample") is False:
             raise NotImplementedError("generate_sample samples (do_sample=True); greedy decoding is generate()")
         if (kwargs.get("num_beams") or 1) != 1:
@@ -277,10 +299,20 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
         sampling = dict(do_sample=True, temperature=float(pick(temperature, "temperature", 1.0)), top_k=int(pick(top_k, "top_k", 0)),
                         top_p=float(pick(top_p, "top_p", 1.0)), seed=int(seed), stream=int(stream))
-        return self._generate(inputs, images, kwargs, sampling=sampling)
+        return self._generate(inputs, images, kwargs, sampling=sampling, processors=processors)
 
-    def _generate(self, inputs, images, kwargs, num_beams=1, length_penalty=1.0, sampling=None):
-        """The argument handling generate, generate_beam and generate_sample share, then Engine.generate."""
+    def _generate(self, inputs, images, kwargs, num_beams=1, length_penalty=1.0, sampling=None, processors=None):
+        """The argument handling generate, generate_beam and generate_sample share, then Engine.generate.  processors: the logits
+        processors as Engine.generate's keywords (the eval runners pass their flags); None: those of generation_config - none under beams,
+        which only refuse what is given outright."""
+        off = {"repetition_penalty": 1.0, "no_repeat_ngram_size": 0, "min_new_tokens": 0}
+        if processors is None:
+            processors = self._processors() if num_beams == 1 else {}
+        else:
+            processors = {k: v for k, v in processors.items() if v is not None and v != off[k]}
+        if num_beams > 1 and processors:
+            raise NotImplementedError("repetition_penalty / no_repeat_ngram_size / min_new_tokens cannot be combined with beams: transformers applies "
+                                      "them to the log-softmax scores inside its beam search and a beam's history follows its parent - not built")
         if kwargs.get("use_cache") is False:
             raise NotImplementedError("use_cache=False: the engine always decodes through its KV cache")
         am = kwargs.get("attention_mask")
@@ -299,6 +331,8 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
         if int(max_new) > room:
             warnings.warn(f"max_new_tokens {max_new} cut to {room}: prompt of {S} rows in an engine of {self.engine.cfg.llm.max_pos} "
                           "positions (config.v3d_max_positions raises the capacity)")
+        if int(max_new) > room and processors.get("min_new_tokens", 0) > room:         # the cut above bounds min_new_tokens with it
+            processors = dict(processors, min_new_tokens=max(room, 0))
         max_new = min(int(max_new), room)
         crit = kwargs.get("stopping_criteria")
         stopping = None
@@ -309,7 +343,7 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
         beams = dict(num_beams=num_beams, length_penalty=length_penalty) if num_beams > 1 else {}
         out = self.engine.generate(ids, frames, coords, max_new_tokens=max_new, eos_token_id=self._eos(kwargs.get("eos_token_id")),
                                    stopping=stopping, box_input=box_input if box_input is not None and len(box_input) else None,
-                                   coord_token_id=coord_ids[0] if coord_ids else None, **beams, **(sampling or {}))
+                                   coord_token_id=coord_ids[0] if coord_ids else None, **beams, **(sampling or {}), **processors)
         return out.view(1, -1)
 
     def prepare_inputs_for_generation(self, *a, **kw):

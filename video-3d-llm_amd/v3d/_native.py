@@ -153,6 +153,8 @@ SIGNATURES = {
     "v3d_sample_rows": (c_i, [c_p, c_l, c_i, c_i, c_i, c_f, c_i, c_f, c_u64, c_i, c_p, c_p, c_p, c_p, c_l, c_p]),
     "v3d_sample_rows_host": (c_i, [c_p, c_l, c_i, c_i, c_f, c_i, c_f, c_u64, c_i, c_p, c_p, c_p]),
     "v3d_philox4x32_10_host": (c_i, [c_p, c_p, c_p]),
+    "v3d_logits_process_rows": (c_i, [c_p, c_l, c_i, c_i, c_i, c_p, c_l, c_i, c_f, c_i, c_i, c_p, c_i, c_p]),
+    "v3d_logits_process_rows_host": (c_i, [c_p, c_l, c_i, c_i, c_i, c_p, c_l, c_i, c_f, c_i, c_i, c_p, c_i]),
     "v3d_lora_down": (c_i, [c_p, c_l, c_p, c_l, c_f, c_p, c_l, c_l, c_i, c_i, c_i, c_p]),
     "v3d_lora_wgrad_chunk": (c_l, [c_l, c_i, c_i]),
     "v3d_lora_wgrad_workspace_bytes": (c_l, [c_l, c_i, c_i]),

@@ -731,7 +731,7 @@ class Engine:
     @torch.no_grad()
     def generate(self, input_ids, images, world_coords, max_new_tokens=16, eos_token_id=None, stopping=None, box_input=None,
                  coord_token_id=None, num_beams=1, length_penalty=1.0, return_trace=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, stream=0,
-                 return_logits=False):
+                 return_logits=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
         """Greedy decoding of one (scene, question): LlavaQwenForCausalLM.generate (llava_qwen.py:208-236)
         with do_sample=False, num_beams=1 as model_scanqa.py:173-185 calls it.  eos_token_id: an int or a collection of ints;
         stopping: optional host callback(token_ids_so_far: LongTensor [n]) -> bool, checked after every token (HF's
@@ -739,9 +739,13 @@ class Engine:
         num_beams > 1 (the drivers' --num_beams): the same prefill, then beam_search (length_penalty, return_trace: see there);
         stopping callbacks cannot be combined with beams.
         do_sample: every token is drawn on the device instead (_sampler: temperature, top_k, top_p, seed, stream; return_logits).  Not
+        with num_beams > 1.
+        repetition_penalty / no_repeat_ngram_size / min_new_tokens: the logits processors (_processors), applied on the device to the
+        logits every token is chosen from - greedy or sampled; with return_logits the result is (ids, the RAW logits [n, 1, V]).  Not
         with num_beams > 1."""
         self._check_beams(num_beams, stopping, return_trace)
-        sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, [stream], num_beams, return_logits)
+        proc = self._processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, max_new_tokens, num_beams, return_logits and not do_sample)
+        sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, [stream], num_beams, return_logits and (do_sample or proc is None))
         feats = self.encode_images(images)
         ids = self.voxel_ids(world_coords.to(self.dtype))
         x = self.build_inputs_embeds(input_ids, feats, ids, box_input=box_input, coord_token_id=coord_token_id)
@@ -750,7 +754,50 @@ class Engine:
         logits = self.llm_forward(x, 0, last_rows=[S - 1])
         if num_beams > 1:
             return self.beam_search(logits, S, num_beams, max_new_tokens, eos_token_id, length_penalty, return_trace)
-        return self.decode_loop(logits, S, max_new_tokens, eos_token_id, stopping, sampler=sampler)
+        return self.decode_loop(logits, S, max_new_tokens, eos_token_id, stopping, sampler=sampler, processors=proc)
+
+    def _processors(self, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, eos=None, max_new_tokens=None, num_beams=1, return_logits=False):
+        """The logits processors of one generation call, checked once: None when all three are off (repetition_penalty 1.0,
+        no_repeat_ngram_size 0, min_new_tokens 0: the loops then run untouched - no launch, no allocation), else the arguments of
+        ops.logits_process_rows ("Logits processors, stated once") with the EOS ids on the device.  A row's history
+        is the tokens it has generated so far - the loop's own device token buffer - never the prompt.  eos: the call's eos_token_id.
+        return_logits (greedy calls; a sampled call keeps them on its sampler): the call also returns the raw [n_steps, M, V] logits,
+        copied BEFORE the processors change them."""
+        try:
+            p = float(repetition_penalty)
+        except (TypeError, ValueError):
+            p = float("nan")
+        if not (p > 0.0 and math.isfinite(p)):
+            raise V3DError(f"repetition_penalty must be a finite float > 0 (got {repetition_penalty!r}; 1.0 is off)")
+        for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_new_tokens", min_new_tokens)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise V3DError(f"{name} must be an integer >= 0 (got {v!r}; 0 is off)")
+        n, k = int(no_repeat_ngram_size), int(min_new_tokens)
+        if p == 1.0 and n == 0 and k == 0:
+            return None
+        if num_beams != 1:
+            raise V3DError("repetition_penalty / no_repeat_ngram_size / min_new_tokens cannot be combined with num_beams > 1: transformers applies "
+                           "them to the log-softmax scores inside its beam search, v3d_beam_topk forms those scores inside the kernel and a beam's "
+                           "history follows its parent - processors under beams are not built")
+        ids = _eos_ids(eos)
+        if k > 0:
+            if not ids:
+                raise V3DError(f"min_new_tokens = {k} needs an eos_token_id: it bans the EOS ids, and none is given")
+            if max_new_tokens is not None and k > max_new_tokens:
+                raise V3DError(f"min_new_tokens = {k} exceeds max_new_tokens = {max_new_tokens}")
+        pr = SceneContext()
+        pr.p, pr.n, pr.k = p, n, k
+        pr.eos = torch.tensor(ids, dtype=torch.int64).to(self.device) if k > 0 else None
+        pr.return_logits, pr.logits = bool(return_logits), None
+        return pr
+
+    @staticmethod
+    def _keeper(sampler, processors):
+        """the state object that asked for the raw logits of the steps (its .logits receives them), or None"""
+        for s in (sampler, processors):
+            if s is not None and s.return_logits:
+                return s
+        return None
 
     def _sampler(self, do_sample, temperature, top_k, top_p, seed, streams, num_beams=1, return_logits=False):
         """The sampling arguments of one generation call, checked once: None for do_sample=False (the greedy code runs untouched), else
@@ -821,7 +868,8 @@ class Engine:
 
     @torch.no_grad()
     def answer(self, question_ids, max_new_tokens=16, eos_token_id=None, stopping=None, num_beams=1, length_penalty=1.0, return_trace=False,
-               box_input=None, coord_token_id=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, stream=0, return_logits=False):
+               box_input=None, coord_token_id=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, stream=0, return_logits=False,
+               repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
         """Greedy answer to one question about the scene prefilled by prefill_scene: only the question's rows (the ids that follow
         the prefix in the full prompt) run through the decoder, at positions P.., attending to the cached prefix; then the
         usual decode loop.  Causality makes the prefix rows of the uncached pass independent of the question, so the tokens are
@@ -829,9 +877,11 @@ class Engine:
         num_beams > 1: beam_search behind the same question rows, as generate does.
         box_input [x, y, z] + coord_token_id (Scan2Cap): the PE of the discretised box centre on the question's <coord> rows, as
         build_inputs_embeds adds it for a whole prompt.
-        do_sample: as generate (stream: this question's stream id, the one answer_group would give it)."""
+        do_sample: as generate (stream: this question's stream id, the one answer_group would give it).
+        repetition_penalty / no_repeat_ngram_size / min_new_tokens: as generate."""
         self._check_beams(num_beams, stopping, return_trace)
-        sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, [stream], num_beams, return_logits)
+        proc = self._processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, max_new_tokens, num_beams, return_logits and not do_sample)
+        sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, [stream], num_beams, return_logits and (do_sample or proc is None))
         P = getattr(self.ctx, "prefix_len", 0)
         if not P or self.ctx.kv_len < P:
             raise V3DError("answer() needs prefill_scene() on this context first")
@@ -849,7 +899,7 @@ class Engine:
         logits = self.llm_forward(x, P, last_rows=[Q - 1])
         if num_beams > 1:
             return self.beam_search(logits, P + Q, num_beams, max_new_tokens, eos_token_id, length_penalty, return_trace)
-        return self.decode_loop(logits, P + Q, max_new_tokens, eos_token_id, stopping, sampler=sampler)
+        return self.decode_loop(logits, P + Q, max_new_tokens, eos_token_id, stopping, sampler=sampler, processors=proc)
 
     MAX_GROUP = 32          # scenes / questions whose decode steps share a pass over the weights (r04: 32; csrc DEC_MAX_ROWS)
 
@@ -954,7 +1004,7 @@ class Engine:
 
     @torch.no_grad()
     def answer_group(self, questions, max_new_tokens=16, eos_token_id=None, box_inputs=None, coord_token_id=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0,
-                     streams=None, return_logits=False):
+                     streams=None, return_logits=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
         """Up to 32 questions about the scene prefilled by prefill_scene, answered together: the cached prefix K/V is handed to
         each question's own cache (one broadcast copy per layer), the questions' rows run through the decoder as ONE batch
         (one pass over the weights; rows padded to the longest question, which causality keeps from affecting the real rows),
@@ -962,8 +1012,14 @@ class Engine:
         A question's rows do not depend on the others (tests/test_gpu_scene_reuse.py: equal to answer() on it alone).
         box_inputs / coord_token_id (Scan2Cap): question_embeds - each question's box-centre PE on its <coord> rows.
         do_sample: every row draws from its own stream (streams: one id per question, default its index), so a question's answer is
-        the one answer(..., stream=id) draws; with return_logits the result is (answers, logits [n_steps, G, V])."""
-        sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, self._streams(streams, len(questions)), 1, return_logits)
+        the one answer(..., stream=id) draws; with return_logits the result is (answers, logits [n_steps, G, V]).
+        repetition_penalty / no_repeat_ngram_size / min_new_tokens: the logits processors, each row over its own generated tokens (one
+        launch per step for the whole group): a row's history and choice are its own, exactly, whatever rows share the launch
+        (tests/test_gpu_logits_engine.py: the same questions in other row positions give the same answers).  Against answer() or another
+        group size the raw logits differ in their last bits (other f32 summation orders), so tokens agree up to near-ties of the
+        processed logits, as greedy tokens do."""
+        proc = self._processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, max_new_tokens, 1, return_logits and not do_sample)
+        sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, self._streams(streams, len(questions)), 1, return_logits and (do_sample or proc is None))
         scene, st, x, P, lens, Sq, share = self._question_rows("answer_group", questions, max_new_tokens, box_inputs, coord_token_id)
         G = len(questions)
         last = torch.tensor([g * Sq + lens[g] - 1 for g in range(G)], dtype=torch.int64, device=self.device)
@@ -974,10 +1030,10 @@ class Engine:
         for c, n in zip(ctxs, lens):
             c.kv_len = P + n
         toks = self.decode_group(rows, ctxs, [P + n for n in lens], max_new_tokens, logits_ready=True, shared_prefix=P if share else 0,
-                                 eos_token_id=eos_token_id, prefix_kv=scene.kv if share else None, sampler=sampler)
+                                 eos_token_id=eos_token_id, prefix_kv=scene.kv if share else None, sampler=sampler, processors=proc)
         self.use(scene)
         out = [r.to(self.device) for r in self.trim_at_eos(toks, eos_token_id)]
-        return (out, sampler.logits) if return_logits else out
+        return (out, self._keeper(sampler, proc).logits) if return_logits else out
 
     def _streams(self, streams, n):
         streams = list(range(n)) if streams is None else list(streams)
@@ -1014,15 +1070,17 @@ class Engine:
         return torch.stack([self.ground_head(query[g: g + 1], scene.ground_of) for g in range(G)])
 
     @torch.no_grad()
-    def generate_group(self, samples, max_new_tokens=16, eos_token_id=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, streams=None, return_logits=False):
+    def generate_group(self, samples, max_new_tokens=16, eos_token_id=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, streams=None, return_logits=False,
+                       repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
         """Throughput form of `generate` for up to 32 (input_ids, images, world_coords) samples: each is prefilled into its
         own context, then all decode together (one pass over the weights per step).  Returns a list of token-id tensors,
         each cut after its first EOS like `generate` does.  The contexts and the row buffers are cached on the engine.
-        do_sample: as answer_group (streams: one id per sample, default its index)."""
+        do_sample: as answer_group (streams: one id per sample, default its index); the logits processors likewise."""
         n = len(samples)
         if not 1 <= n <= self.MAX_GROUP:
             raise V3DError(f"generate_group takes 1 to {self.MAX_GROUP} samples")
-        sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, self._streams(streams, n), 1, return_logits)
+        proc = self._processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, max_new_tokens, 1, return_logits and not do_sample)
+        sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, self._streams(streams, n), 1, return_logits and (do_sample or proc is None))
         pool = self.__dict__.setdefault("_group_ctxs", [])
         while len(pool) < n:
             pool.append(self.new_context())
@@ -1042,9 +1100,9 @@ class Engine:
                 lens.append(x.shape[0])
         finally:
             self.use(keep)
-        toks = self.decode_group(grp, pool[:n], lens, max_new_tokens, eos_token_id=eos_token_id, sampler=sampler)
+        toks = self.decode_group(grp, pool[:n], lens, max_new_tokens, eos_token_id=eos_token_id, sampler=sampler, processors=proc)
         out = [r.to(self.device) for r in self.trim_at_eos(toks, eos_token_id)]
-        return (out, sampler.logits) if return_logits else out
+        return (out, self._keeper(sampler, proc).logits) if return_logits else out
 
     # ------------------------------------------------------------------ scenes decoding together
     def new_group(self, n_scenes):
@@ -1096,7 +1154,7 @@ class Engine:
         return g.logits[:M, : l.vocab]
 
     def decode_group(self, g, ctxs, prompt_lens, max_new_tokens, logits_ready=False, shared_prefix=0, eos_token_id=None, lookahead=2, prefix_kv=None,
-                     do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, streams=None, return_logits=False, sampler=None):
+                     do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, streams=None, return_logits=False, sampler=None, processors=None):
         """Greedy decoding of M prefilled scenes together (their prefill logits are in ctx.logits[0], or already in g.logits
         with logits_ready); returns the token ids [M, n_steps] (device), n_steps <= max_new_tokens.
         eos_token_id (int or ints): the stop test runs on the device (v3d_eos_update: a done mask per row and their count); the
@@ -1106,7 +1164,9 @@ class Engine:
         Without eos_token_id all max_new_tokens steps run.
         do_sample (or a sampler built by _sampler): ops.sample_rows stands where ops.argmax_rows does, step counted from 0, row m on
         streams[m] (default m); nothing else in the loop changes.  With return_logits the logits of the executed steps are left in
-        sampler.logits [n_steps, M, V] (and returned beside the tokens when this method built the sampler)."""
+        sampler.logits [n_steps, M, V] (and returned beside the tokens when this method built the sampler).
+        processors (built by _processors): one ops.logits_process_rows launch per step, directly in front of the token choice and behind
+        the copy return_logits takes, over the rows of `toks` written so far - row m's history is toks[:step, m]."""
         l = self.cfg.llm
         M = len(ctxs)
         if M > g.n:
@@ -1116,7 +1176,8 @@ class Engine:
             sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, self._streams(streams, M), 1, return_logits)
         if sampler is not None and sampler.streams.numel() != M:
             raise V3DError("decode_group: one sampling stream id per row")
-        keep = torch.empty((max_new_tokens, M, l.vocab), dtype=self.dtype, device=self.device) if sampler is not None and sampler.return_logits else None
+        keeper = self._keeper(sampler, processors)
+        keep = torch.empty((max_new_tokens, M, l.vocab), dtype=self.dtype, device=self.device) if keeper is not None else None
         self._check_room(max(prompt_lens), max_new_tokens)
         toks = torch.empty((max_new_tokens, M), dtype=torch.int64, device=self.device)
         if not logits_ready:
@@ -1129,11 +1190,13 @@ class Engine:
             st.done[:M].zero_()
         n_steps = max_new_tokens
         for step in range(max_new_tokens):
+            if keep is not None:
+                keep[step].copy_(logits)
+            if processors is not None:
+                ops.logits_process_rows(logits, toks, step, processors.p, processors.n, processors.k, processors.eos)
             if sampler is None:
                 ops.argmax_rows(logits, toks[step], g.amax_ws)
             else:
-                if keep is not None:
-                    keep[step].copy_(logits)
                 ops.sample_rows(logits, toks[step], sampler.ws, sampler.T, sampler.top_k, sampler.top_p, sampler.seed, step, sampler.streams)
             if eos:
                 ops.eos_update(toks[step], st.eos, st.done[:M], st.n_done)
@@ -1145,9 +1208,9 @@ class Engine:
             ops.embed_gather(self.embed, toks[step], out=g.x[:M])
             logits = self.decode_forward_rows(g, ctxs, [S + step for S in prompt_lens], shared_prefix=shared_prefix, prefix_kv=prefix_kv)
         if keep is not None:
-            sampler.logits = keep[:n_steps]
+            keeper.logits = keep[:n_steps]
             if own:
-                return toks[:n_steps].t(), sampler.logits
+                return toks[:n_steps].t(), keeper.logits
         return toks[:n_steps].t()
 
     @staticmethod
@@ -1190,17 +1253,18 @@ class Engine:
         return out
 
     def decode_loop(self, logits, S, max_new_tokens, eos_token_id=None, stopping=None, lookahead=2, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, stream=0,
-                    return_logits=False, sampler=None):
+                    return_logits=False, sampler=None, processors=None):
         """Greedy loop of one scene; token ids stay on the device (argmax kernel -> embedding gather).  EOS: the stop test runs on
         the device and the host reads it `lookahead` - 1 steps late (as decode_group does), so the launch queue never drains; the
         returned ids end with the first EOS.  A stopping callback (HF stopping_criteria) forces one host synchronisation per step.
         do_sample (or a sampler built by _sampler): ops.sample_rows stands where ops.argmax does, step counted from 0 on `stream`;
-        with return_logits the result is (ids, logits [n, 1, V])."""
+        with return_logits the result is (ids, logits [n, 1, V]).
+        processors (built by _processors): one ops.logits_process_rows launch per step in front of the token choice, as in decode_group."""
         self._check_room(S, max_new_tokens)
         if sampler is None and do_sample:
             sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, [stream], 1, return_logits)
-        keep = None
-        if sampler is not None and sampler.return_logits:
+        keep, keeper = None, self._keeper(sampler, processors)
+        if keeper is not None:
             keep = torch.empty((max_new_tokens, 1, self.cfg.llm.vocab), dtype=self.dtype, device=self.device)
         eos = _eos_ids(eos_token_id)
         toks = torch.empty(max_new_tokens, dtype=torch.int64, device=self.device)
@@ -1210,12 +1274,15 @@ class Engine:
             st.done[:1].zero_()
         n = 0
         for step in range(max_new_tokens):
-            if sampler is None:
-                ops.argmax(logits, toks[step: step + 1])
-            else:
+            if sampler is not None or processors is not None:
                 row = logits.reshape(1, -1)[:, : self.cfg.llm.vocab]
                 if keep is not None:
                     keep[step].copy_(row)
+                if processors is not None:
+                    ops.logits_process_rows(row, toks, step, processors.p, processors.n, processors.k, processors.eos)
+            if sampler is None:
+                ops.argmax(logits, toks[step: step + 1])
+            else:
                 ops.sample_rows(row, toks[step: step + 1], sampler.ws, sampler.T, sampler.top_k, sampler.top_p, sampler.seed, step, sampler.streams)
             n = step + 1
             if st is not None:
@@ -1234,8 +1301,8 @@ class Engine:
         if st is not None:
             out = self.trim_at_eos(out[None], eos)[0].to(self.device)
         if keep is not None:
-            sampler.logits = keep[: out.numel()]
-            return out, sampler.logits
+            keeper.logits = keep[: out.numel()]
+            return out, keeper.logits
         return out
 
     # ------------------------------------------------------------------ beam search (a23, num_beams > 1)

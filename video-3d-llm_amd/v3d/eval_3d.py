@@ -27,6 +27,8 @@ The records keep their keys and order; sharding defaults to whole scenes per ran
 --reuse-scenes one scene prefill and Engine.answer(num_beams=N) per question.  The cross-scene decode group is not used with beams.
 --temperature T > 0 (with --top_p, --top_k, --seed; generation tasks): every token is drawn by the device sampler, each question from the
 random stream numbered by its index in the question file, so the records do not depend on batching, --reuse-scenes or the rank count.
+--repetition_penalty P --no_repeat_ngram_size N --min_new_tokens K (generation tasks): the device logits processors over each answer's own
+tokens, greedy or sampled, on every path; not with --num_beams > 1.
 
 `v3d.eval_ground`, `v3d.eval_scan2cap`, `v3d.eval_sqa3d` are entry points with the task fixed.
 """
@@ -213,14 +215,15 @@ def ground_answer_fn(task, model, tokenizer, image_processor, video_processor, m
 
 
 def answer_fn_for(task, model, tokenizer, image_processor, video_processor, model_name, a, pool=None, times=None, stats=None, sampling=None,
-                  stream_fn=None):
+                  stream_fn=None, processors=None):
     if task in GROUND_TASKS:
         return ground_answer_fn(task, model, tokenizer, image_processor, video_processor, model_name, a.max_frame_num,
                                 workers=(0 if a.loader_workers < 0 else a.loader_workers or None), pool=pool, stats=stats,
                                 reuse_scenes=a.reuse_scenes, pipeline=not a.no_pipeline)
     kw = dict(max_frame_num=a.max_frame_num, max_new_tokens=a.max_new_tokens, reuse_scenes=a.reuse_scenes, times=times,
               pipeline=not a.no_pipeline, group_size=a.decode_group, workers=(0 if a.loader_workers < 0 else a.loader_workers or None),
-              pool=pool, stats=stats, num_beams=a.num_beams, length_penalty=a.length_penalty, sampling=sampling, stream_fn=stream_fn)
+              pool=pool, stats=stats, num_beams=a.num_beams, length_penalty=a.length_penalty, sampling=sampling, stream_fn=stream_fn,
+              processors=processors)
     if task == "scan2cap":                      # model_scan2cap.py:137-139, 199-212
         def record(line, text):
             r = E.make_record(line, text, model_name)
@@ -257,6 +260,7 @@ def main(argv=None, task=None):
     ap.add_argument("--n_gpu", type=int, default=None, help="the reference's flag: started plainly with N > 1, launch N ranks of this runner")
     E.add_beam_arguments(ap)
     E.add_sampling_arguments(ap)
+    E.add_processor_arguments(ap)
     a = ap.parse_args(argv)
     fixed_task = task
     task = task or a.task
@@ -265,6 +269,9 @@ def main(argv=None, task=None):
     E.sampling_arguments(ap, a)
     if a.num_beams > 1 and task in GROUND_TASKS:
         ap.error("--num_beams belongs to the generation tasks (scanqa, sqa3d, scan2cap)")
+    processors = E.processor_arguments(ap, a)
+    if processors and task in GROUND_TASKS:
+        ap.error("--repetition_penalty / --no_repeat_ngram_size / --min_new_tokens belong to the generation tasks (scanqa, sqa3d, scan2cap)")
     if os.path.exists(a.answer_file):
         print(f"The {a.answer_file} already exists!!!")
         return 0
@@ -289,7 +296,7 @@ def main(argv=None, task=None):
     vp = VideoProcessor(video_folder=a.video_folder, annotation_dir=a.embodiedscan_folder, frame_sampling_strategy=a.frame_sampling_strategy,
                         metadata_dir=a.metadata_folder)
     times = []
-    fn = answer_fn_for(task, model, tokenizer, image_processor, vp, name, a, pool=pool, times=times, sampling=sampling, stream_fn=stream_fn)
+    fn = answer_fn_for(task, model, tokenizer, image_processor, vp, name, a, pool=pool, times=times, sampling=sampling, stream_fn=stream_fn, processors=processors)
     records = E.evaluate(questions, fn, rank, world, gather_dev, shard=a.shard or ("scene" if a.reuse_scenes else "stride"))
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(a.answer_file)), exist_ok=True)

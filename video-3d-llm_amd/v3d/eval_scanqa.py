@@ -165,7 +165,7 @@ def default_workers():
 
 def model_answer_fn(model, tokenizer, image_processor, video_processor, model_name, max_frame_num=32, max_new_tokens=512,
                     reuse_scenes=False, times=None, pipeline=True, group_size=16, workers=None, stats=None, record_fn=None, pool=None,
-                    box_input_fn=None, skip_fn=None, num_beams=1, length_penalty=1.0, sampling=None, stream_fn=None):
+                    box_input_fn=None, skip_fn=None, num_beams=1, length_penalty=1.0, sampling=None, stream_fn=None, processors=None):
     """The per-rank loop of model_scanqa.py:130-206 around `model` (the loader-produced LlavaQwenForCausalLM).
     reuse_scenes: one scene prefill per run of consecutive questions about a scene (pipelined or, with pipeline=False, synchronous).
     pipeline (default): v3d.pipeline - asynchronous host loader, prefill / grouped-decode overlap, device-side stop test; the
@@ -181,7 +181,17 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
     sampling = dict(temperature, top_k, top_p, seed) (the drivers' --temperature > 0): every token is drawn by the device sampler -
     model.generate_sample per question, or with reuse_scenes one scene prefill and Engine.answer_group(do_sample=True) per batch.
     stream_fn(line) -> the question's sampling stream id (its index in the question file), so a record does not depend on batching,
-    on reuse_scenes or on the number of ranks.  Not with num_beams > 1."""
+    on reuse_scenes or on the number of ranks.  Not with num_beams > 1.
+    processors = dict(repetition_penalty, no_repeat_ngram_size, min_new_tokens) holding the controls that are on (the drivers'
+    --repetition_penalty / --no_repeat_ngram_size / --min_new_tokens): the device logits processors on every path, greedy or sampled -
+    a row's history is its own generated tokens whatever it is batched with; the paths' raw logits still differ in their last bits (the
+    one-row and the row kernels sum in another order), so records agree between batchings and reuse_scenes up to near-ties of the
+    processed logits, as the greedy records do.  Where a long prompt cuts max_new_tokens to the engine's room, min_new_tokens is cut with
+    it (fit_processors).  Not with num_beams > 1.
+    They are passed to the model explicitly, so a run without the flags ignores generation_config's, as it always has."""
+    proc = dict(processors or {})
+    if proc and num_beams > 1:
+        raise ValueError("repetition_penalty / no_repeat_ngram_size / min_new_tokens cannot be combined with num_beams > 1: processors under beams are not built")
     if sampling and num_beams > 1:
         raise ValueError("sampling (temperature > 0) cannot be combined with num_beams > 1: beam-sample is not built")
     if sampling and stream_fn is None:
@@ -211,14 +221,14 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
                 with torch.inference_mode():
                     if sampling:
                         toks = model.generate_sample(ids, images=images, modalities="video", num_beams=1, max_new_tokens=max_new_tokens,
-                                                     use_cache=True, video_dict=vd, stream=stream_fn(line), **sampling)
+                                                     use_cache=True, video_dict=vd, stream=stream_fn(line), processors=proc, **sampling)
                     elif num_beams > 1:
                         toks = model.generate_beam(ids, images=images, modalities="video", do_sample=False, temperature=0.0, top_p=None,
                                                    num_beams=num_beams, length_penalty=length_penalty, max_new_tokens=max_new_tokens,
-                                                   use_cache=True, video_dict=vd)
+                                                   use_cache=True, video_dict=vd, processors=proc)
                     else:
                         toks = model.generate(ids, images=images, modalities="video", do_sample=False, temperature=0.0, top_p=None, num_beams=1,
-                                              max_new_tokens=max_new_tokens, use_cache=True, video_dict=vd)
+                                              max_new_tokens=max_new_tokens, use_cache=True, video_dict=vd, processors=proc)
                 if times is not None:
                     torch.cuda.synchronize()
                     times.append(time.time() - t0)
@@ -263,7 +273,7 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
                         continue
                     draw = dict(do_sample=True, streams=[stream_fn(l) for l in lines[b: b + len(qs)]], **sampling) if sampling else {}
                     answers = eng.answer_group(qs, max_new_tokens=min(max_new_tokens, room), eos_token_id=eos, box_inputs=boxes,
-                                               coord_token_id=coord_id, **draw)
+                                               coord_token_id=coord_id, **draw, **fit_processors(proc, min(max_new_tokens, room)))
                     out += [decode(a) for a in answers]
             i = j
         return out
@@ -305,7 +315,7 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
         room = eng.cfg.llm.max_pos - (max((len(p) for p in prompts), default=1) - 1 + n_vis) + 1
         t0 = time.time()
         try:
-            toks = pipe.run(samples(), min(max_new_tokens, room), eos_token_id=model._eos())
+            toks = pipe.run(samples(), min(max_new_tokens, room), eos_token_id=model._eos(), processors=proc or None)
         finally:
             loader.close()
         if times is not None and lines:
@@ -357,7 +367,7 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
 
         t0 = time.time()
         try:
-            answers = pipe.run(scenes(), max_new_tokens, eos_token_id=model._eos())
+            answers = pipe.run(scenes(), max_new_tokens, eos_token_id=model._eos(), processors=proc or None)
         finally:
             loader.close()
         if times is not None and lines:
@@ -399,6 +409,36 @@ def sampling_arguments(ap, a, questions=None):
         ap.error("--temperature > 0 cannot be combined with --num_beams > 1: beam-sample is not built")
     index = {id(q): i for i, q in enumerate(questions or [])}
     return dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed), (lambda line: index[id(line)])
+
+
+def fit_processors(processors, max_new_tokens):
+    """processors with min_new_tokens bounded by the max_new_tokens a call actually runs (the runners cut it to the engine's room)"""
+    if processors and processors.get("min_new_tokens", 0) > max_new_tokens:
+        return dict(processors, min_new_tokens=max(int(max_new_tokens), 0))
+    return processors
+
+
+def add_processor_arguments(ap):
+    ap.add_argument("--repetition_penalty", type=float, default=1.0,
+                    help="the logits of every token generated so far are divided (positive) or multiplied (negative) by this (transformers' "
+                         "repetition_penalty; 1: off)")
+    ap.add_argument("--no_repeat_ngram_size", type=int, default=0,
+                    help="no n-gram of this size occurs twice in an answer (the reference drivers' commented-out no_repeat_ngram_size=3; 0: off)")
+    ap.add_argument("--min_new_tokens", type=int, default=0, help="the EOS ids cannot be chosen before this many tokens (0: off)")
+
+
+def processor_arguments(ap, a):
+    """`processors` of model_answer_fn from the parsed flags: the controls that are on ({} when none is)."""
+    if not a.repetition_penalty > 0 or a.repetition_penalty == float("inf") or a.no_repeat_ngram_size < 0 or a.min_new_tokens < 0:
+        ap.error("--repetition_penalty > 0, --no_repeat_ngram_size >= 0, --min_new_tokens >= 0")
+    if a.min_new_tokens > a.max_new_tokens:
+        ap.error("--min_new_tokens exceeds --max-new-tokens")
+    proc = {k: v for k, v, off in (("repetition_penalty", a.repetition_penalty, 1.0), ("no_repeat_ngram_size", a.no_repeat_ngram_size, 0),
+                                   ("min_new_tokens", a.min_new_tokens, 0)) if v != off}
+    if proc and a.num_beams > 1:
+        ap.error("--repetition_penalty / --no_repeat_ngram_size / --min_new_tokens cannot be combined with --num_beams > 1: transformers applies them "
+                 "to the log-softmax scores inside its beam search and a beam's history follows its parent - not built")
+    return proc
 
 
 def add_beam_arguments(ap):
@@ -461,8 +501,10 @@ def main(argv=None):
                     help="the reference's flag (model_scanqa.py:222): started plainly with N > 1, launch N ranks of this runner on this node")
     add_beam_arguments(ap)
     add_sampling_arguments(ap)
+    add_processor_arguments(ap)
     a = ap.parse_args(argv)
     sampling_arguments(ap, a)
+    processors = processor_arguments(ap, a)
     if os.path.exists(a.answer_file):                                                         # model_scanqa.py:238-240
         print(f"The {a.answer_file} already exists!!!")
         return 0
@@ -485,7 +527,7 @@ def main(argv=None):
     times = []
     fn = model_answer_fn(model, tokenizer, image_processor, vp, name, a.max_frame_num, a.max_new_tokens, a.reuse_scenes, times,
                          pipeline=not a.no_pipeline, group_size=a.decode_group, workers=(0 if a.loader_workers < 0 else a.loader_workers or None), pool=pool,
-                         num_beams=a.num_beams, length_penalty=a.length_penalty, sampling=sampling, stream_fn=stream_fn)
+                         num_beams=a.num_beams, length_penalty=a.length_penalty, sampling=sampling, stream_fn=stream_fn, processors=processors)
     records = evaluate(questions, fn, rank, world, gather_dev, shard=a.shard or ("scene" if a.reuse_scenes else "stride"))
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(a.answer_file)), exist_ok=True)

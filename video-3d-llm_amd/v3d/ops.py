@@ -1084,6 +1084,62 @@ def philox4x32_10_host(counter, key):
     return [int(v) & 0xFFFFFFFF for v in o.tolist()]
 
 
+# ------------------------------------------------------------------------------ logits processors (csrc/logits.hip, csrc/logits_rule.h)
+
+LOGITS_MAX_M, LOGITS_MAX_HISTORY = 32, 8192
+
+
+def _logits_history(what, history, M, n_prev, cuda):
+    """(history or None, its step stride): row m's j-th generated token is history[j, m] (or history[j] for one row)"""
+    n_prev = int(n_prev)
+    if n_prev < 0:
+        raise V3DError(f"{what}: n_prev < 0")
+    if history is None:
+        if n_prev:
+            raise V3DError(f"{what}: n_prev = {n_prev} without a history")
+        return None, M
+    h = history if history.dim() == 2 else history[:, None]
+    if h.dtype != torch.int64 or h.is_cuda != cuda or h.dim() != 2 or h.shape[1] < M or h.shape[0] < n_prev or (h.shape[1] > 1 and h.stride(1) != 1) or \
+            (h.shape[0] > 1 and h.stride(0) < M):
+        raise V3DError(f"{what}: history is int64 [>= n_prev, >= M] with unit column stride on the logits' side (got {tuple(history.shape)} {history.dtype}, "
+                       f"n_prev={n_prev}, M={M})")
+    return h, (h.stride(0) if h.shape[0] > 1 else max(M, 1))
+
+
+def logits_process_rows(logits, history, n_prev, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, eos_ids=None, V=None):
+    """logits [M, >=V] 16-bit rows, changed IN PLACE by the logits processors (DESIGN section 2, "Logits processors, stated once";
+    v3d_logits_process_rows) over each row's generated tokens history[0:n_prev, m] (device int64 [steps, >= M]; [steps] for one row):
+    repetition_penalty, then no_repeat_ngram_size, then min_new_tokens (eos_ids: device int64 [n]).  Columns past V are not touched."""
+    x = logits if logits.dim() == 2 else logits[None]
+    M = x.shape[0]
+    V = x.shape[1] if V is None else int(V)
+    if not x.is_cuda or x.stride(1) != 1 or x.shape[1] < V:
+        raise V3DError(f"logits_process_rows: logits {tuple(x.shape)} on {x.device}")
+    h, ld = _logits_history("logits_process_rows", history, M, n_prev, True)
+    if eos_ids is not None and (eos_ids.dtype != torch.int64 or not eos_ids.is_cuda or not eos_ids.is_contiguous()):
+        raise V3DError("logits_process_rows: eos_ids is a contiguous device int64 [n]")
+    check(lib().v3d_logits_process_rows(_p(x), x.stride(0), M, V, _code(x), _p(h), ld, int(n_prev), float(repetition_penalty), int(no_repeat_ngram_size),
+                                        int(min_new_tokens), _p(eos_ids), 0 if eos_ids is None else eos_ids.numel(), _stream()), "v3d_logits_process_rows")
+    return logits
+
+
+def logits_process_rows_host(logits, dtype, history, n_prev, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, eos_ids=None, V=None):
+    """The host twin (v3d_logits_process_rows_host): logits f32 [M, >=V] (host) holding values of `dtype` (torch.float16 / torch.bfloat16),
+    changed in place; history / eos_ids host int64."""
+    x = logits if logits.dim() == 2 else logits[None]
+    if x.is_cuda or x.dtype != torch.float32 or x.stride(1) != 1:
+        raise V3DError("logits_process_rows_host: host f32 rows")
+    M = x.shape[0]
+    V = x.shape[1] if V is None else int(V)
+    if x.shape[1] < V:
+        raise V3DError("logits_process_rows_host: V exceeds the row")
+    h, ld = _logits_history("logits_process_rows_host", history, M, n_prev, False)
+    e = None if eos_ids is None else torch.as_tensor(eos_ids, dtype=torch.int64).contiguous()
+    check(lib().v3d_logits_process_rows_host(_p(x), x.stride(0), M, V, _DT[dtype], _p(h), ld, int(n_prev), float(repetition_penalty), int(no_repeat_ngram_size),
+                                             int(min_new_tokens), _p(e), 0 if e is None else e.numel()), "v3d_logits_process_rows_host")
+    return logits
+
+
 # ------------------------------------------------------------------------------ grounding
 
 

@@ -292,10 +292,15 @@ class ScenePipeline:
 
     # ------------------------------------------------------------------ the whole list
     @torch.no_grad()
-    def run(self, samples, max_new_tokens, eos_token_id=None, overlap=True, stamps=None, trim=True):
+    def run(self, samples, max_new_tokens, eos_token_id=None, overlap=True, stamps=None, trim=True, processors=None):
         """samples: iterable of SceneSample (consumed lazily, one decode group ahead).  Returns one host LongTensor of new token ids
-        per sample, in order, cut after its first EOS (trim=False: the untrimmed [n, steps] rows per group, for benchmarking)."""
+        per sample, in order, cut after its first EOS (trim=False: the untrimmed [n, steps] rows per group, for benchmarking).
+        processors: dict(repetition_penalty, no_repeat_ngram_size, min_new_tokens) or None - Engine._processors, handed to every group's
+        decode (all rows of a group start at step 0, so a row's history is its column of the group's token buffer)."""
         eng, G = self.eng, self.G
+        if processors and processors.get("min_new_tokens", 0) > max_new_tokens:          # the caller cut max_new_tokens to the engine's room
+            processors = dict(processors, min_new_tokens=max_new_tokens)
+        proc = eng._processors(eos=eos_token_id, max_new_tokens=max_new_tokens, **processors) if processors else None
         sA, sB = self.streams
         it = iter(samples)
         keep = eng.ctx
@@ -344,7 +349,7 @@ class ScenePipeline:
                 with torch.cuda.stream(sB if overlap else torch.cuda.current_stream()):
                     for ev in pre_done:
                         torch.cuda.current_stream().wait_event(ev)
-                    toks = eng.decode_group(self.groups[gi % 2], ctxs, lens, max_new_tokens, eos_token_id=eos_token_id)
+                    toks = eng.decode_group(self.groups[gi % 2], ctxs, lens, max_new_tokens, eos_token_id=eos_token_id, processors=proc)
                     out += eng.trim_at_eos(toks, eos_token_id) if trim else [toks.cpu()]
                 gi += 1
             if overlap:
@@ -384,10 +389,11 @@ class SceneReusePipeline:
         return self.inputs.upload_seconds
 
     @torch.no_grad()
-    def run(self, scenes, max_new_tokens, eos_token_id=None, overlap=True):
+    def run(self, scenes, max_new_tokens, eos_token_id=None, overlap=True, processors=None):
         """scenes: iterable of (SceneSample whose input_ids are the PREFIX ids up to and including <image>, [question id tensors] or a
         SceneJob) - consumed lazily, one scene ahead.  Returns, per scene, the list of its answers' token-id tensors (host, cut after the
-        first EOS) or, for a grounding job, of its queries' score vectors (host).  A scene without questions is prefilled and gives []."""
+        first EOS) or, for a grounding job, of its queries' score vectors (host).  A scene without questions is prefilled and gives [].
+        processors: dict(repetition_penalty, no_repeat_ngram_size, min_new_tokens) or None, handed to every answer_group call."""
         eng = self.eng
         keep_ctx, keep_ws = eng.ctx, eng.ws
         it = iter(scenes)
@@ -436,10 +442,13 @@ class SceneReusePipeline:
                             answers += list(eng.ground_group(qs, job.ground_rows[b0: b0 + self.batch]).cpu())
                             continue
                         room = eng.cfg.llm.max_pos - P - max(int(q.numel()) for q in qs) + 1
+                        proc = dict(processors or {})
+                        if proc.get("min_new_tokens", 0) > min(max_new_tokens, room):         # cut with max_new_tokens
+                            proc["min_new_tokens"] = max(min(max_new_tokens, room), 0)
                         answers += [a.cpu() for a in eng.answer_group(
                             qs, max_new_tokens=min(max_new_tokens, room), eos_token_id=eos_token_id,
                             box_inputs=None if job.box_inputs is None else job.box_inputs[b0: b0 + self.batch],
-                            coord_token_id=job.coord_token_id)]
+                            coord_token_id=job.coord_token_id, **proc)]
                     read[k % 2] = sB.record_event()
                 out.append(answers)
             if overlap:
