@@ -16,6 +16,7 @@ import logits_check as lc
 import sample_check as sc
 from oracle import pipeline_oracle as PO
 from v3d._native import V3DError
+from v3d.generation import GenerationRule
 
 pytestmark = pytest.mark.gpu
 
@@ -163,7 +164,8 @@ def test_neutral_values_give_todays_tokens(world):
     w, eng = world, world.eng
     got = eng.generate(w.prompt, w.images, w.coords, max_new_tokens=NEW, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0)
     assert torch.equal(got.cpu(), w.greedy)
-    assert eng._processors(1.0, 0, 0, None) is None and eng._processors(1, 0, 0, 5, 4, 3) is None
+    off = dict(repetition_penalty=1, no_repeat_ngram_size=0, min_new_tokens=0)
+    assert eng._choice(GenerationRule(**dict(off, repetition_penalty=1.0)), None) is None and eng._choice(GenerationRule(num_beams=3, **off), 5, 4) is None
     with pytest.raises(V3DError):                          # nothing to return the logits of: plain greedy decoding keeps no copy
         eng.generate(w.prompt, w.images, w.coords, max_new_tokens=4, return_logits=True)
 

@@ -36,6 +36,7 @@ from llava.model.multimodal_encoder.siglip_encoder import SigLipVisionTower
 from v3d import loader
 from v3d._native import V3DError
 from v3d.engine import Engine
+from v3d.generation import OFF, GenerationRule, processors_on
 from v3d.token_ids import IMAGE_TOKEN_INDEX
 
 
@@ -64,7 +65,6 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
     config_class = LlavaQwenConfig
     _GENERATE_KW = {"max_new_tokens", "do_sample", "num_beams", "temperature", "top_p", "top_k", "use_cache", "attention_mask",
                     "position_ids", "stopping_criteria", "eos_token_id", "pad_token_id", "video_dict", "max_length"}
-    _PROCESSOR_KW = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens")        # read from generation_config (_processors)
 
     def __init__(self, config, state_dict=None, dtype=torch.float16, device=None, llm_fp8=False, max_frames=32, llm_fp4=False):
         super().__init__()
@@ -175,24 +175,26 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
         return e
 
     def _unknown(self, what, kwargs):
-        unknown = set(kwargs) - self._GENERATE_KW
-        if unknown:
+        extra = set(kwargs) - self._GENERATE_KW
+        if extra:
             hint = ""
-            if unknown & set(self._PROCESSOR_KW):
-                hint = (f"; {sorted(unknown & set(self._PROCESSOR_KW))} are read from model.generation_config "
+            if extra & set(OFF):                       # the logits processors: read from generation_config (_rule)
+                hint = (f"; {sorted(extra & set(OFF))} are read from model.generation_config "
                         "(e.g. model.generation_config.no_repeat_ngram_size = 3), not from keywords")
-            raise TypeError(f"LlavaQwenForCausalLM.{what}: unsupported arguments {sorted(unknown)} (accepted: {sorted(self._GENERATE_KW)}){hint}")
+            raise TypeError(f"LlavaQwenForCausalLM.{what}: unsupported arguments {sorted(extra)} (accepted: {sorted(self._GENERATE_KW)}){hint}")
 
-    def _processors(self):
-        """The logits processors of generation_config (the checkpoint's generation_config.json, or what the caller has set on
-        model.generation_config), as Engine.generate's keywords; a missing or None entry is off (1.0 / 0 / 0), as in transformers."""
-        gc = getattr(self, "generation_config", None)
-        out = {}
-        for name, off, cast in (("repetition_penalty", 1.0, float), ("no_repeat_ngram_size", 0, int), ("min_new_tokens", 0, int)):
-            v = getattr(gc, name, None)
-            if v is not None and v != off:
-                out[name] = cast(v)
-        return out
+    def _rule(self, processors, num_beams=1, **fields):
+        """The GenerationRule of one generate / generate_beam / generate_sample call.  processors: the logits processors given outright as
+        a dict (the eval runners pass their flags; a missing or None entry is off); None: those of generation_config (the checkpoint's
+        generation_config.json, or what the caller has set on model.generation_config) - none under beams, which only refuse what is
+        given outright."""
+        if processors is None:
+            processors = getattr(self, "generation_config", None) if num_beams == 1 else {}
+        on = processors_on(processors)
+        if num_beams > 1 and on:
+            raise NotImplementedError("repetition_penalty / no_repeat_ngram_size / min_new_tokens cannot be combined with beams: transformers applies "
+                                      "them to the log-softmax scores inside its beam search and a beam's history follows its parent - not built")
+        return GenerationRule(num_beams=max(num_beams, 1), **fields, **on)          # (num_beams < 1 has always decoded greedily here)
 
     def _sample(self, input_ids, images, video_dict):
         if input_ids is None or input_ids.shape[0] != 1:
@@ -260,7 +262,7 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
             raise NotImplementedError("greedy decoding only (the 3-D eval drivers run temperature 0, num_beams 1); beam search is "
                                       "generate_beam(input_ids, images=..., video_dict=..., num_beams=N), sampling is "
                                       "generate_sample(input_ids, images=..., video_dict=..., temperature=T, top_p=p, top_k=k, seed=s)")
-        return self._generate(inputs, images, kwargs, processors=processors)
+        return self._generate(inputs, images, kwargs, self._rule(processors))
 
     @torch.no_grad()
     def generate_beam(self, inputs=None, images=None, image_sizes=None, modalities=("image",), num_beams=1, length_penalty=1.0, processors=None, **kwargs):
@@ -273,7 +275,7 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
             raise NotImplementedError("beam search here is deterministic (do_sample=False)")
         if int(num_beams) > 1 and kwargs.get("stopping_criteria"):
             raise NotImplementedError("stopping_criteria cannot be combined with beams: they stop by EOS ids and max_new_tokens only")
-        return self._generate(inputs, images, kwargs, num_beams=int(num_beams), length_penalty=float(length_penalty), processors=processors)
+        return self._generate(inputs, images, kwargs, self._rule(processors, int(num_beams), length_penalty=float(length_penalty)))
 
     @torch.no_grad()
     def generate_sample(self, inputs=None, images=None, image_sizes=None, modalities=("image",), temperature=None, top_p=None, top_k=None, seed=None,
@@ -297,22 +299,12 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
             return default if v is None else v
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
-        sampling = dict(do_sample=True, temperature=float(pick(temperature, "temperature", 1.0)), top_k=int(pick(top_k, "top_k", 0)),
-                        top_p=float(pick(top_p, "top_p", 1.0)), seed=int(seed), stream=int(stream))
-        return self._generate(inputs, images, kwargs, sampling=sampling, processors=processors)
+        rule = self._rule(processors, do_sample=True, temperature=float(pick(temperature, "temperature", 1.0)), top_k=int(pick(top_k, "top_k", 0)),
+                          top_p=float(pick(top_p, "top_p", 1.0)), seed=int(seed))
+        return self._generate(inputs, images, kwargs, rule, stream=int(stream))
 
-    def _generate(self, inputs, images, kwargs, num_beams=1, length_penalty=1.0, sampling=None, processors=None):
-        """The argument handling generate, generate_beam and generate_sample share, then Engine.generate.  processors: the logits
-        processors as Engine.generate's keywords (the eval runners pass their flags); None: those of generation_config - none under beams,
-        which only refuse what is given outright."""
-        off = {"repetition_penalty": 1.0, "no_repeat_ngram_size": 0, "min_new_tokens": 0}
-        if processors is None:
-            processors = self._processors() if num_beams == 1 else {}
-        else:
-            processors = {k: v for k, v in processors.items() if v is not None and v != off[k]}
-        if num_beams > 1 and processors:
-            raise NotImplementedError("repetition_penalty / no_repeat_ngram_size / min_new_tokens cannot be combined with beams: transformers applies "
-                                      "them to the log-softmax scores inside its beam search and a beam's history follows its parent - not built")
+    def _generate(self, inputs, images, kwargs, rule, stream=0):
+        """The argument handling generate, generate_beam and generate_sample share, then Engine.generate under `rule` (_rule)."""
         if kwargs.get("use_cache") is False:
             raise NotImplementedError("use_cache=False: the engine always decodes through its KV cache")
         am = kwargs.get("attention_mask")
@@ -331,8 +323,7 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
         if int(max_new) > room:
             warnings.warn(f"max_new_tokens {max_new} cut to {room}: prompt of {S} rows in an engine of {self.engine.cfg.llm.max_pos} "
                           "positions (config.v3d_max_positions raises the capacity)")
-        if int(max_new) > room and processors.get("min_new_tokens", 0) > room:         # the cut above bounds min_new_tokens with it
-            processors = dict(processors, min_new_tokens=max(room, 0))
+            rule = rule.fit(room)                                                      # the cut bounds min_new_tokens with it
         max_new = min(int(max_new), room)
         crit = kwargs.get("stopping_criteria")
         stopping = None
@@ -340,10 +331,9 @@ class LlavaQwenForCausalLM(nn.Module, LlavaMetaForCausalLM):
             stopping = lambda toks: any(bool(torch.as_tensor(c(toks[None], None)).any()) for c in crit)      # noqa: E731
         box_input = video_dict.get("box_input") if hasattr(video_dict, "get") else None
         coord_ids = getattr(self.config, "coord_token_ids", None)
-        beams = dict(num_beams=num_beams, length_penalty=length_penalty) if num_beams > 1 else {}
         out = self.engine.generate(ids, frames, coords, max_new_tokens=max_new, eos_token_id=self._eos(kwargs.get("eos_token_id")),
                                    stopping=stopping, box_input=box_input if box_input is not None and len(box_input) else None,
-                                   coord_token_id=coord_ids[0] if coord_ids else None, **beams, **(sampling or {}), **processors)
+                                   coord_token_id=coord_ids[0] if coord_ids else None, stream=stream, rule=rule)
         return out.view(1, -1)
 
     def prepare_inputs_for_generation(self, *a, **kw):

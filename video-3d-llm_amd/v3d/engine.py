@@ -19,6 +19,7 @@ import torch
 
 from . import ops
 from ._native import V3DError
+from .generation import eos_ids as _eos_ids, rule_of
 from .linears import Linears
 
 
@@ -134,12 +135,6 @@ def random_state_dict(cfg: EngineConfig, dtype, device, seed=0, std=0.02, ground
     return sd
 
 
-def _eos_ids(eos_token_id):
-    """eos_token_id (None, an int or a collection of ints) -> tuple of ints"""
-    ids = () if eos_token_id is None else (eos_token_id,) if isinstance(eos_token_id, int) else eos_token_id
-    return tuple(int(e) for e in ids)
-
-
 def _pad2(w, rows, cols):
     out = torch.zeros((rows, cols), dtype=w.dtype, device=w.device)
     out[: w.shape[0], : w.shape[1]] = w
@@ -155,6 +150,23 @@ def _pad1(b, n):
 class SceneContext:
     """Buffers that belong to one (scene, question) in flight: inputs_embeds / residual stream, KV cache,
     last-row hidden + logits, the decode step's row buffers and split-KV workspace."""
+
+
+class TokenChoice:
+    """What stands between the logits and the token of every step of one generation call that is not plain greedy decoding
+    (Engine._choice builds it): the processors' arguments, the sampler's, and the raw logits the call keeps for return_logits."""
+    keep = logits = None          # keep [max_new_tokens, rows, V]: allocated by the loop for return_logits; logits = its executed steps
+
+    def step(self, rows, toks, step, out):
+        """One step on the logits `rows` [M, V]: copy the raw rows if kept, the processors over the rows' histories toks[:step], then the
+        draw into `out`.  False when the rule does not sample: the loop's own argmax chooses from the processed rows."""
+        if self.keep is not None:
+            self.keep[step].copy_(rows)
+        if self.processors:
+            ops.logits_process_rows(rows, toks, step, self.p, self.n, self.k, self.eos)
+        if self.sampling:
+            ops.sample_rows(rows, out, self.ws, self.T, self.top_k, self.top_p, self.seed, step, self.streams)
+        return self.sampling
 
 
 class Engine:
@@ -730,111 +742,53 @@ class Engine:
     # ------------------------------------------------------------------ generate (a23)
     @torch.no_grad()
     def generate(self, input_ids, images, world_coords, max_new_tokens=16, eos_token_id=None, stopping=None, box_input=None,
-                 coord_token_id=None, num_beams=1, length_penalty=1.0, return_trace=False, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, stream=0,
-                 return_logits=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
+                 coord_token_id=None, stream=0, rule=None, **controls):
         """Greedy decoding of one (scene, question): LlavaQwenForCausalLM.generate (llava_qwen.py:208-236)
         with do_sample=False, num_beams=1 as model_scanqa.py:173-185 calls it.  eos_token_id: an int or a collection of ints;
         stopping: optional host callback(token_ids_so_far: LongTensor [n]) -> bool, checked after every token (HF's
         stopping_criteria; forces one host synchronisation per step).
-        num_beams > 1 (the drivers' --num_beams): the same prefill, then beam_search (length_penalty, return_trace: see there);
-        stopping callbacks cannot be combined with beams.
-        do_sample: every token is drawn on the device instead (_sampler: temperature, top_k, top_p, seed, stream; return_logits).  Not
-        with num_beams > 1.
-        repetition_penalty / no_repeat_ngram_size / min_new_tokens: the logits processors (_processors), applied on the device to the
-        logits every token is chosen from - greedy or sampled; with return_logits the result is (ids, the RAW logits [n, 1, V]).  Not
-        with num_beams > 1."""
-        self._check_beams(num_beams, stopping, return_trace)
-        proc = self._processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, max_new_tokens, num_beams, return_logits and not do_sample)
-        sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, [stream], num_beams, return_logits and (do_sample or proc is None))
+        rule (a v3d.generation.GenerationRule, or its fields as keywords: num_beams, do_sample, repetition_penalty, ...): beams, sampling,
+        the logits processors and return_logits, described there.  With num_beams > 1 the same prefill, then beam_search; a sampled
+        row draws from the random stream `stream`; with return_logits the result is (ids, the RAW logits [n, 1, V])."""
+        choice = self._choice(rule := rule_of(rule, controls), eos_token_id, max_new_tokens, [stream], stopping)
         feats = self.encode_images(images)
         ids = self.voxel_ids(world_coords.to(self.dtype))
         x = self.build_inputs_embeds(input_ids, feats, ids, box_input=box_input, coord_token_id=coord_token_id)
         S = x.shape[0]
         self._check_room(S, max_new_tokens)
         logits = self.llm_forward(x, 0, last_rows=[S - 1])
-        if num_beams > 1:
-            return self.beam_search(logits, S, num_beams, max_new_tokens, eos_token_id, length_penalty, return_trace)
-        return self.decode_loop(logits, S, max_new_tokens, eos_token_id, stopping, sampler=sampler, processors=proc)
+        if rule.num_beams > 1:
+            return self.beam_search(logits, S, rule.num_beams, max_new_tokens, eos_token_id, rule.length_penalty, rule.return_trace)
+        return self.decode_loop(logits, S, max_new_tokens, eos_token_id, stopping, choice=choice)
 
-    def _processors(self, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, eos=None, max_new_tokens=None, num_beams=1, return_logits=False):
-        """The logits processors of one generation call, checked once: None when all three are off (repetition_penalty 1.0,
-        no_repeat_ngram_size 0, min_new_tokens 0: the loops then run untouched - no launch, no allocation), else the arguments of
-        ops.logits_process_rows ("Logits processors, stated once") with the EOS ids on the device.  A row's history
-        is the tokens it has generated so far - the loop's own device token buffer - never the prompt.  eos: the call's eos_token_id.
-        return_logits (greedy calls; a sampled call keeps them on its sampler): the call also returns the raw [n_steps, M, V] logits,
-        copied BEFORE the processors change them."""
-        try:
-            p = float(repetition_penalty)
-        except (TypeError, ValueError):
-            p = float("nan")
-        if not (p > 0.0 and math.isfinite(p)):
-            raise V3DError(f"repetition_penalty must be a finite float > 0 (got {repetition_penalty!r}; 1.0 is off)")
-        for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_new_tokens", min_new_tokens)):
-            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
-                raise V3DError(f"{name} must be an integer >= 0 (got {v!r}; 0 is off)")
-        n, k = int(no_repeat_ngram_size), int(min_new_tokens)
-        if p == 1.0 and n == 0 and k == 0:
+    def _choice(self, rule, eos_token_id=None, max_new_tokens=None, streams=None, stopping=None):
+        """The device state of one generation call under `rule` (v3d.generation.GenerationRule), checked against the call once: None
+        for plain greedy decoding and for beams (the loops then run untouched - no launch, no allocation), else a TokenChoice: the
+        arguments of ops.logits_process_rows with the EOS ids on the device, those of ops.sample_rows with the rows' stream ids and the
+        engine's one sampling workspace (the loop allocates the buffer return_logits fills).  streams: one id per row (needed to sample);
+        token n of a row is drawn at step n of its stream, so its tokens depend on its logits, the seed and its stream id only."""
+        rule.check(eos_token_id, max_new_tokens, stopping)
+        if rule.plain:
             return None
-        if num_beams != 1:
-            raise V3DError("repetition_penalty / no_repeat_ngram_size / min_new_tokens cannot be combined with num_beams > 1: transformers applies "
-                           "them to the log-softmax scores inside its beam search, v3d_beam_topk forms those scores inside the kernel and a beam's "
-                           "history follows its parent - processors under beams are not built")
-        ids = _eos_ids(eos)
-        if k > 0:
-            if not ids:
-                raise V3DError(f"min_new_tokens = {k} needs an eos_token_id: it bans the EOS ids, and none is given")
-            if max_new_tokens is not None and k > max_new_tokens:
-                raise V3DError(f"min_new_tokens = {k} exceeds max_new_tokens = {max_new_tokens}")
-        pr = SceneContext()
-        pr.p, pr.n, pr.k = p, n, k
-        pr.eos = torch.tensor(ids, dtype=torch.int64).to(self.device) if k > 0 else None
-        pr.return_logits, pr.logits = bool(return_logits), None
-        return pr
-
-    @staticmethod
-    def _keeper(sampler, processors):
-        """the state object that asked for the raw logits of the steps (its .logits receives them), or None"""
-        for s in (sampler, processors):
-            if s is not None and s.return_logits:
-                return s
-        return None
-
-    def _sampler(self, do_sample, temperature, top_k, top_p, seed, streams, num_beams=1, return_logits=False):
-        """The sampling arguments of one generation call, checked once: None for do_sample=False (the greedy code runs untouched), else
-        the rule's arguments ("Sampling, stated once"), the rows' stream ids on the device and the engine's one
-        sampling workspace.  Token n of a row is drawn at step n (0 = from the prefill logits) of the row's stream, so a row's tokens
-        depend on its logits, the seed and its stream id only - not on the rows it is batched with.  return_logits: the call also
-        returns the [n_steps, M, V] logits every token was chosen from."""
-        if not do_sample:
-            if return_logits:
-                raise V3DError("return_logits belongs to do_sample=True")
-            return None
-        if num_beams != 1:
-            raise V3DError("do_sample cannot be combined with num_beams > 1: beam-sample is not built")
-        T, p = float(temperature), float(top_p)
-        if not (T > 0.0 and math.isfinite(T)) or not (0.0 < p <= 1.0) or int(top_k) != top_k or top_k < 0:
-            raise V3DError(f"do_sample needs a finite temperature > 0, top_k >= 0 and 0 < top_p <= 1 (got {temperature!r}, {top_k!r}, {top_p!r})")
-        streams = [int(v) for v in streams]
-        if any(not 0 <= v < (1 << 31) for v in streams):
-            raise V3DError("a sampling stream id is an integer in [0, 2^31)")
-        sp = SceneContext()
-        sp.T, sp.top_k, sp.top_p, sp.seed = T, int(top_k), p, int(seed) & 0xFFFFFFFFFFFFFFFF
-        sp.streams = torch.tensor(streams, dtype=torch.int32).to(self.device)
-        ws = self.__dict__.get("_sample_ws")
-        if ws is None or ws[0] != self.cfg.llm.vocab:                              # (the vocabulary can grow: grow_vocab)
-            ws = self._sample_ws = (self.cfg.llm.vocab, ops.sample_workspace(self.MAX_GROUP, self.cfg.llm.vocab, self.device))
-        ws = ws[1]
-        sp.ws, sp.return_logits, sp.logits = ws, bool(return_logits), None
-        return sp
-
-    @staticmethod
-    def _check_beams(num_beams, stopping, return_trace=False):
-        if not isinstance(num_beams, int) or num_beams < 1:
-            raise V3DError(f"num_beams must be a positive integer (got {num_beams!r})")
-        if num_beams > 1 and stopping is not None:
-            raise V3DError("a stopping callback cannot be combined with num_beams > 1: beams stop by EOS ids and max_new_tokens only")
-        if num_beams == 1 and return_trace:
-            raise V3DError("return_trace belongs to beam search (num_beams > 1)")
+        if streams is None and rule.do_sample:
+            raise V3DError("do_sample needs the call's rows: one sampling stream id per row")
+        ch = TokenChoice()
+        ch.return_logits = rule.return_logits
+        ch.p, ch.n, ch.k = float(rule.repetition_penalty), rule.no_repeat_ngram_size, rule.min_new_tokens
+        ch.processors = bool(rule.processors)
+        ch.eos = torch.tensor(_eos_ids(eos_token_id), dtype=torch.int64).to(self.device) if ch.k > 0 else None
+        ch.sampling = rule.do_sample
+        if rule.do_sample:
+            streams = [int(v) for v in streams]
+            if any(not 0 <= v < (1 << 31) for v in streams):
+                raise V3DError("a sampling stream id is an integer in [0, 2^31)")
+            ch.T, ch.top_k, ch.top_p, ch.seed = float(rule.temperature), int(rule.top_k), float(rule.top_p), int(rule.seed) & 0xFFFFFFFFFFFFFFFF
+            ch.streams = torch.tensor(streams, dtype=torch.int32).to(self.device)
+            ws = self.__dict__.get("_sample_ws")
+            if ws is None or ws[0] != self.cfg.llm.vocab:                              # (the vocabulary can grow: grow_vocab)
+                ws = self._sample_ws = (self.cfg.llm.vocab, ops.sample_workspace(self.MAX_GROUP, self.cfg.llm.vocab, self.device))
+            ch.ws = ws[1]
+        return ch
 
     # ------------------------------------------------------------------ scene-level reuse (SURVEY 8 f1)
     @torch.no_grad()
@@ -867,21 +821,16 @@ class Engine:
         return self.ctx.prefix_len
 
     @torch.no_grad()
-    def answer(self, question_ids, max_new_tokens=16, eos_token_id=None, stopping=None, num_beams=1, length_penalty=1.0, return_trace=False,
-               box_input=None, coord_token_id=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, stream=0, return_logits=False,
-               repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
+    def answer(self, question_ids, max_new_tokens=16, eos_token_id=None, stopping=None, box_input=None, coord_token_id=None, stream=0, rule=None, **controls):
         """Greedy answer to one question about the scene prefilled by prefill_scene: only the question's rows (the ids that follow
         the prefix in the full prompt) run through the decoder, at positions P.., attending to the cached prefix; then the
         usual decode loop.  Causality makes the prefix rows of the uncached pass independent of the question, so the tokens are
         those of generate(prefix_ids + question_ids, ...) (tests/test_gpu_scene_reuse.py).  The prefix rows are left intact.
-        num_beams > 1: beam_search behind the same question rows, as generate does.
         box_input [x, y, z] + coord_token_id (Scan2Cap): the PE of the discretised box centre on the question's <coord> rows, as
         build_inputs_embeds adds it for a whole prompt.
-        do_sample: as generate (stream: this question's stream id, the one answer_group would give it).
-        repetition_penalty / no_repeat_ngram_size / min_new_tokens: as generate."""
-        self._check_beams(num_beams, stopping, return_trace)
-        proc = self._processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, max_new_tokens, num_beams, return_logits and not do_sample)
-        sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, [stream], num_beams, return_logits and (do_sample or proc is None))
+        rule / its fields as keywords: as generate - beam_search behind the same question rows with num_beams > 1; stream: this
+        question's sampling stream id, the one answer_group would give it."""
+        choice = self._choice(rule := rule_of(rule, controls), eos_token_id, max_new_tokens, [stream], stopping)
         P = getattr(self.ctx, "prefix_len", 0)
         if not P or self.ctx.kv_len < P:
             raise V3DError("answer() needs prefill_scene() on this context first")
@@ -897,9 +846,9 @@ class Engine:
                 pe = self.centre_pe(torch.as_tensor(box_input, dtype=torch.float32).to(device=self.device, dtype=self.dtype).reshape(-1, 3)[:1].contiguous())[0]
                 ops.add_row(x, torch.tensor(rows, dtype=torch.int64, device=self.device), pe)
         logits = self.llm_forward(x, P, last_rows=[Q - 1])
-        if num_beams > 1:
-            return self.beam_search(logits, P + Q, num_beams, max_new_tokens, eos_token_id, length_penalty, return_trace)
-        return self.decode_loop(logits, P + Q, max_new_tokens, eos_token_id, stopping, sampler=sampler, processors=proc)
+        if rule.num_beams > 1:
+            return self.beam_search(logits, P + Q, rule.num_beams, max_new_tokens, eos_token_id, rule.length_penalty, rule.return_trace)
+        return self.decode_loop(logits, P + Q, max_new_tokens, eos_token_id, stopping, choice=choice)
 
     MAX_GROUP = 32          # scenes / questions whose decode steps share a pass over the weights (r04: 32; csrc DEC_MAX_ROWS)
 
@@ -1003,23 +952,21 @@ class Engine:
         return scene, st, x, P, lens, Sq, share
 
     @torch.no_grad()
-    def answer_group(self, questions, max_new_tokens=16, eos_token_id=None, box_inputs=None, coord_token_id=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0,
-                     streams=None, return_logits=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
+    def answer_group(self, questions, max_new_tokens=16, eos_token_id=None, box_inputs=None, coord_token_id=None, streams=None, rule=None, **controls):
         """Up to 32 questions about the scene prefilled by prefill_scene, answered together: the cached prefix K/V is handed to
         each question's own cache (one broadcast copy per layer), the questions' rows run through the decoder as ONE batch
         (one pass over the weights; rows padded to the longest question, which causality keeps from affecting the real rows),
         then all answers decode as one group (decode_group).  Returns a list of token-id tensors, each cut after its first EOS.
         A question's rows do not depend on the others (tests/test_gpu_scene_reuse.py: equal to answer() on it alone).
         box_inputs / coord_token_id (Scan2Cap): question_embeds - each question's box-centre PE on its <coord> rows.
-        do_sample: every row draws from its own stream (streams: one id per question, default its index), so a question's answer is
-        the one answer(..., stream=id) draws; with return_logits the result is (answers, logits [n_steps, G, V]).
-        repetition_penalty / no_repeat_ngram_size / min_new_tokens: the logits processors, each row over its own generated tokens (one
-        launch per step for the whole group): a row's history and choice are its own, exactly, whatever rows share the launch
+        rule / its fields as keywords (v3d.generation.GenerationRule; no beams): a sampled row draws from its own stream (streams: one id
+        per question, default its index), so a question's answer is the one answer(..., stream=id) draws; with return_logits the
+        result is (answers, logits [n_steps, G, V]).  The logits processors run each row over its own generated tokens (one launch per
+        step for the whole group): a row's history and choice are its own, exactly, whatever rows share the launch
         (tests/test_gpu_logits_engine.py: the same questions in other row positions give the same answers).  Against answer() or another
         group size the raw logits differ in their last bits (other f32 summation orders), so tokens agree up to near-ties of the
         processed logits, as greedy tokens do."""
-        proc = self._processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, max_new_tokens, 1, return_logits and not do_sample)
-        sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, self._streams(streams, len(questions)), 1, return_logits and (do_sample or proc is None))
+        rule, choice = self._group_choice("answer_group", rule, controls, eos_token_id, max_new_tokens, streams, len(questions))
         scene, st, x, P, lens, Sq, share = self._question_rows("answer_group", questions, max_new_tokens, box_inputs, coord_token_id)
         G = len(questions)
         last = torch.tensor([g * Sq + lens[g] - 1 for g in range(G)], dtype=torch.int64, device=self.device)
@@ -1030,16 +977,20 @@ class Engine:
         for c, n in zip(ctxs, lens):
             c.kv_len = P + n
         toks = self.decode_group(rows, ctxs, [P + n for n in lens], max_new_tokens, logits_ready=True, shared_prefix=P if share else 0,
-                                 eos_token_id=eos_token_id, prefix_kv=scene.kv if share else None, sampler=sampler, processors=proc)
+                                 eos_token_id=eos_token_id, prefix_kv=scene.kv if share else None, choice=choice)
         self.use(scene)
         out = [r.to(self.device) for r in self.trim_at_eos(toks, eos_token_id)]
-        return (out, self._keeper(sampler, proc).logits) if return_logits else out
+        return (out, choice.logits) if rule.return_logits else out
 
-    def _streams(self, streams, n):
+    def _group_choice(self, what, rule, controls, eos_token_id, max_new_tokens, streams, n):
+        """(rule, choice) of answer_group / generate_group: n rows that decode together, row m on streams[m] (default m)"""
+        rule = rule_of(rule, controls, beams=False)
+        if rule.num_beams > 1:
+            raise V3DError(f"{what} decodes its rows together, greedily or sampled: num_beams > 1 runs one question at a time (generate, answer)")
         streams = list(range(n)) if streams is None else list(streams)
         if len(streams) != n:
             raise V3DError(f"streams: one sampling stream id per row ({len(streams)} for {n} rows)")
-        return streams
+        return rule, self._choice(rule, eos_token_id, max_new_tokens, streams)
 
     @torch.no_grad()
     def ground_group(self, questions, ground_rows):
@@ -1070,17 +1021,15 @@ class Engine:
         return torch.stack([self.ground_head(query[g: g + 1], scene.ground_of) for g in range(G)])
 
     @torch.no_grad()
-    def generate_group(self, samples, max_new_tokens=16, eos_token_id=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, streams=None, return_logits=False,
-                       repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
+    def generate_group(self, samples, max_new_tokens=16, eos_token_id=None, streams=None, rule=None, **controls):
         """Throughput form of `generate` for up to 32 (input_ids, images, world_coords) samples: each is prefilled into its
         own context, then all decode together (one pass over the weights per step).  Returns a list of token-id tensors,
         each cut after its first EOS like `generate` does.  The contexts and the row buffers are cached on the engine.
-        do_sample: as answer_group (streams: one id per sample, default its index); the logits processors likewise."""
+        rule / its fields as keywords: as answer_group (streams: one id per sample, default its index)."""
         n = len(samples)
         if not 1 <= n <= self.MAX_GROUP:
             raise V3DError(f"generate_group takes 1 to {self.MAX_GROUP} samples")
-        proc = self._processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, max_new_tokens, 1, return_logits and not do_sample)
-        sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, self._streams(streams, n), 1, return_logits and (do_sample or proc is None))
+        rule, choice = self._group_choice("generate_group", rule, controls, eos_token_id, max_new_tokens, streams, n)
         pool = self.__dict__.setdefault("_group_ctxs", [])
         while len(pool) < n:
             pool.append(self.new_context())
@@ -1100,9 +1049,9 @@ class Engine:
                 lens.append(x.shape[0])
         finally:
             self.use(keep)
-        toks = self.decode_group(grp, pool[:n], lens, max_new_tokens, eos_token_id=eos_token_id, sampler=sampler, processors=proc)
+        toks = self.decode_group(grp, pool[:n], lens, max_new_tokens, eos_token_id=eos_token_id, choice=choice)
         out = [r.to(self.device) for r in self.trim_at_eos(toks, eos_token_id)]
-        return (out, self._keeper(sampler, proc).logits) if return_logits else out
+        return (out, choice.logits) if rule.return_logits else out
 
     # ------------------------------------------------------------------ scenes decoding together
     def new_group(self, n_scenes):
@@ -1153,8 +1102,7 @@ class Engine:
         lin.head(x, g.last[:M], g.logits[:M], fuse=None)
         return g.logits[:M, : l.vocab]
 
-    def decode_group(self, g, ctxs, prompt_lens, max_new_tokens, logits_ready=False, shared_prefix=0, eos_token_id=None, lookahead=2, prefix_kv=None,
-                     do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, streams=None, return_logits=False, sampler=None, processors=None):
+    def decode_group(self, g, ctxs, prompt_lens, max_new_tokens, logits_ready=False, shared_prefix=0, eos_token_id=None, lookahead=2, prefix_kv=None, choice=None):
         """Greedy decoding of M prefilled scenes together (their prefill logits are in ctx.logits[0], or already in g.logits
         with logits_ready); returns the token ids [M, n_steps] (device), n_steps <= max_new_tokens.
         eos_token_id (int or ints): the stop test runs on the device (v3d_eos_update: a done mask per row and their count); the
@@ -1162,22 +1110,17 @@ class Engine:
         drains and the group stops at most `lookahead` - 1 steps after its last row has produced an EOS.  Rows that finished
         earlier keep decoding (their columns are independent); callers cut every row after its first EOS (trim_at_eos).
         Without eos_token_id all max_new_tokens steps run.
-        do_sample (or a sampler built by _sampler): ops.sample_rows stands where ops.argmax_rows does, step counted from 0, row m on
-        streams[m] (default m); nothing else in the loop changes.  With return_logits the logits of the executed steps are left in
-        sampler.logits [n_steps, M, V] (and returned beside the tokens when this method built the sampler).
-        processors (built by _processors): one ops.logits_process_rows launch per step, directly in front of the token choice and behind
-        the copy return_logits takes, over the rows of `toks` written so far - row m's history is toks[:step, m]."""
+        choice (built by _choice; None: plain greedy decoding): TokenChoice.step stands in front of ops.argmax_rows, or with sampling in
+        its place - step counted from 0, row m's history toks[:step, m]; nothing else in the loop changes.  With return_logits the
+        raw logits of the executed steps are left in choice.logits [n_steps, M, V]."""
         l = self.cfg.llm
         M = len(ctxs)
         if M > g.n:
             raise V3DError("decode group too small")
-        own = sampler is None and do_sample
-        if own:
-            sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, self._streams(streams, M), 1, return_logits)
-        if sampler is not None and sampler.streams.numel() != M:
+        if choice is not None and choice.sampling and choice.streams.numel() != M:
             raise V3DError("decode_group: one sampling stream id per row")
-        keeper = self._keeper(sampler, processors)
-        keep = torch.empty((max_new_tokens, M, l.vocab), dtype=self.dtype, device=self.device) if keeper is not None else None
+        if choice is not None and choice.return_logits:
+            choice.keep = torch.empty((max_new_tokens, M, l.vocab), dtype=self.dtype, device=self.device)
         self._check_room(max(prompt_lens), max_new_tokens)
         toks = torch.empty((max_new_tokens, M), dtype=torch.int64, device=self.device)
         if not logits_ready:
@@ -1190,14 +1133,8 @@ class Engine:
             st.done[:M].zero_()
         n_steps = max_new_tokens
         for step in range(max_new_tokens):
-            if keep is not None:
-                keep[step].copy_(logits)
-            if processors is not None:
-                ops.logits_process_rows(logits, toks, step, processors.p, processors.n, processors.k, processors.eos)
-            if sampler is None:
+            if choice is None or not choice.step(logits, toks, step, toks[step]):
                 ops.argmax_rows(logits, toks[step], g.amax_ws)
-            else:
-                ops.sample_rows(logits, toks[step], sampler.ws, sampler.T, sampler.top_k, sampler.top_p, sampler.seed, step, sampler.streams)
             if eos:
                 ops.eos_update(toks[step], st.eos, st.done[:M], st.n_done)
                 if self._late_word(st.host, st.events, st.n_done, step, lookahead) >= M:      # every row had finished by then: the steps
@@ -1207,10 +1144,8 @@ class Engine:
                 break
             ops.embed_gather(self.embed, toks[step], out=g.x[:M])
             logits = self.decode_forward_rows(g, ctxs, [S + step for S in prompt_lens], shared_prefix=shared_prefix, prefix_kv=prefix_kv)
-        if keep is not None:
-            keeper.logits = keep[:n_steps]
-            if own:
-                return toks[:n_steps].t(), keeper.logits
+        if choice is not None and choice.keep is not None:
+            choice.logits = choice.keep[:n_steps]
         return toks[:n_steps].t()
 
     @staticmethod
@@ -1252,20 +1187,15 @@ class Engine:
             out.append(row)
         return out
 
-    def decode_loop(self, logits, S, max_new_tokens, eos_token_id=None, stopping=None, lookahead=2, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, stream=0,
-                    return_logits=False, sampler=None, processors=None):
+    def decode_loop(self, logits, S, max_new_tokens, eos_token_id=None, stopping=None, lookahead=2, choice=None):
         """Greedy loop of one scene; token ids stay on the device (argmax kernel -> embedding gather).  EOS: the stop test runs on
         the device and the host reads it `lookahead` - 1 steps late (as decode_group does), so the launch queue never drains; the
         returned ids end with the first EOS.  A stopping callback (HF stopping_criteria) forces one host synchronisation per step.
-        do_sample (or a sampler built by _sampler): ops.sample_rows stands where ops.argmax does, step counted from 0 on `stream`;
-        with return_logits the result is (ids, logits [n, 1, V]).
-        processors (built by _processors): one ops.logits_process_rows launch per step in front of the token choice, as in decode_group."""
+        choice (built by _choice; None: plain greedy decoding): TokenChoice.step on the one row in front of ops.argmax, or with sampling
+        in its place, as in decode_group; with return_logits the result is (ids, raw logits [n, 1, V])."""
         self._check_room(S, max_new_tokens)
-        if sampler is None and do_sample:
-            sampler = self._sampler(do_sample, temperature, top_k, top_p, seed, [stream], 1, return_logits)
-        keep, keeper = None, self._keeper(sampler, processors)
-        if keeper is not None:
-            keep = torch.empty((max_new_tokens, 1, self.cfg.llm.vocab), dtype=self.dtype, device=self.device)
+        if choice is not None and choice.return_logits:
+            choice.keep = torch.empty((max_new_tokens, 1, self.cfg.llm.vocab), dtype=self.dtype, device=self.device)
         eos = _eos_ids(eos_token_id)
         toks = torch.empty(max_new_tokens, dtype=torch.int64, device=self.device)
         st = None
@@ -1274,16 +1204,8 @@ class Engine:
             st.done[:1].zero_()
         n = 0
         for step in range(max_new_tokens):
-            if sampler is not None or processors is not None:
-                row = logits.reshape(1, -1)[:, : self.cfg.llm.vocab]
-                if keep is not None:
-                    keep[step].copy_(row)
-                if processors is not None:
-                    ops.logits_process_rows(row, toks, step, processors.p, processors.n, processors.k, processors.eos)
-            if sampler is None:
+            if choice is None or not choice.step(logits.reshape(1, -1)[:, : self.cfg.llm.vocab], toks, step, toks[step: step + 1]):
                 ops.argmax(logits, toks[step: step + 1])
-            else:
-                ops.sample_rows(row, toks[step: step + 1], sampler.ws, sampler.T, sampler.top_k, sampler.top_p, sampler.seed, step, sampler.streams)
             n = step + 1
             if st is not None:
                 ops.eos_update(toks[step: step + 1], st.eos, st.done[:1], st.n_done)
@@ -1300,9 +1222,9 @@ class Engine:
         out = toks[:n]
         if st is not None:
             out = self.trim_at_eos(out[None], eos)[0].to(self.device)
-        if keep is not None:
-            keeper.logits = keep[: out.numel()]
-            return out, keeper.logits
+        if choice is not None and choice.keep is not None:
+            choice.logits = choice.keep[: out.numel()]
+            return out, choice.logits
         return out
 
     # ------------------------------------------------------------------ beam search (a23, num_beams > 1)

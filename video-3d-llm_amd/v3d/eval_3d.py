@@ -40,6 +40,7 @@ import time
 import torch
 
 from . import eval_scanqa as E
+from .generation import add_arguments, rule_from_flags
 from .token_ids import IGNORE_INDEX, IMAGE_TOKEN_INDEX
 
 GEN_TASKS = ("scanqa", "sqa3d", "scan2cap")
@@ -214,16 +215,14 @@ def ground_answer_fn(task, model, tokenizer, image_processor, video_processor, m
     return run_reuse if reuse_scenes else run
 
 
-def answer_fn_for(task, model, tokenizer, image_processor, video_processor, model_name, a, pool=None, times=None, stats=None, sampling=None,
-                  stream_fn=None, processors=None):
+def answer_fn_for(task, model, tokenizer, image_processor, video_processor, model_name, a, pool=None, times=None, stats=None, rule=None, stream_fn=None):
     if task in GROUND_TASKS:
         return ground_answer_fn(task, model, tokenizer, image_processor, video_processor, model_name, a.max_frame_num,
                                 workers=(0 if a.loader_workers < 0 else a.loader_workers or None), pool=pool, stats=stats,
                                 reuse_scenes=a.reuse_scenes, pipeline=not a.no_pipeline)
     kw = dict(max_frame_num=a.max_frame_num, max_new_tokens=a.max_new_tokens, reuse_scenes=a.reuse_scenes, times=times,
               pipeline=not a.no_pipeline, group_size=a.decode_group, workers=(0 if a.loader_workers < 0 else a.loader_workers or None),
-              pool=pool, stats=stats, num_beams=a.num_beams, length_penalty=a.length_penalty, sampling=sampling, stream_fn=stream_fn,
-              processors=processors)
+              pool=pool, stats=stats, rule=rule, stream_fn=stream_fn)
     if task == "scan2cap":                      # model_scan2cap.py:137-139, 199-212
         def record(line, text):
             r = E.make_record(line, text, model_name)
@@ -258,20 +257,14 @@ def main(argv=None, task=None):
     ap.add_argument("--llm-weights", choices=E.LLM_WEIGHTS, default="bf16", help="decoder linears: 16-bit (default), e4m3 (fp8) or MXFP4 (fp4); not reference paths")
     ap.add_argument("--lora-path", default=None, help="a LoRA adapter directory merged into the decoder at load (every task)")
     ap.add_argument("--n_gpu", type=int, default=None, help="the reference's flag: started plainly with N > 1, launch N ranks of this runner")
-    E.add_beam_arguments(ap)
-    E.add_sampling_arguments(ap)
-    E.add_processor_arguments(ap)
+    add_arguments(ap)
     a = ap.parse_args(argv)
     fixed_task = task
     task = task or a.task
-    if a.temperature > 0 and task in GROUND_TASKS:
-        ap.error("--temperature belongs to the generation tasks (scanqa, sqa3d, scan2cap)")
-    E.sampling_arguments(ap, a)
-    if a.num_beams > 1 and task in GROUND_TASKS:
-        ap.error("--num_beams belongs to the generation tasks (scanqa, sqa3d, scan2cap)")
-    processors = E.processor_arguments(ap, a)
-    if processors and task in GROUND_TASKS:
-        ap.error("--repetition_penalty / --no_repeat_ngram_size / --min_new_tokens belong to the generation tasks (scanqa, sqa3d, scan2cap)")
+    rule = rule_from_flags(ap, a)
+    if (rule.num_beams > 1 or not rule.plain) and task in GROUND_TASKS:
+        ap.error("--num_beams, --temperature, --repetition_penalty / --no_repeat_ngram_size / --min_new_tokens belong to the generation tasks "
+                 "(scanqa, sqa3d, scan2cap)")
     if os.path.exists(a.answer_file):
         print(f"The {a.answer_file} already exists!!!")
         return 0
@@ -285,8 +278,7 @@ def main(argv=None, task=None):
     with open(os.path.expanduser(a.question_file)) as f:
         questions = json.load(f)[: a.test_size]
     pool = None
-    sampling, stream_fn = E.sampling_arguments(ap, a, questions)
-    if a.loader_workers >= 0 and not (task in GEN_TASKS and (a.no_pipeline or a.num_beams > 1 or sampling)):
+    if a.loader_workers >= 0 and not (task in GEN_TASKS and (a.no_pipeline or rule.num_beams > 1 or rule.do_sample)):
         from . import frame_io
         pool = frame_io.make_pool(a.loader_workers or E.default_workers())          # forked before this process touches the GPU
     rank, world, dev, gather_dev = E.rank_setup(a.n_gpu)
@@ -296,7 +288,7 @@ def main(argv=None, task=None):
     vp = VideoProcessor(video_folder=a.video_folder, annotation_dir=a.embodiedscan_folder, frame_sampling_strategy=a.frame_sampling_strategy,
                         metadata_dir=a.metadata_folder)
     times = []
-    fn = answer_fn_for(task, model, tokenizer, image_processor, vp, name, a, pool=pool, times=times, sampling=sampling, stream_fn=stream_fn, processors=processors)
+    fn = answer_fn_for(task, model, tokenizer, image_processor, vp, name, a, pool=pool, times=times, rule=rule, stream_fn=E.question_streams(questions))
     records = E.evaluate(questions, fn, rank, world, gather_dev, shard=a.shard or ("scene" if a.reuse_scenes else "stride"))
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(a.answer_file)), exist_ok=True)

@@ -28,6 +28,7 @@ import time
 import torch
 
 from . import distributed as D
+from .generation import GenerationRule, add_arguments, rule_from_flags
 from .token_ids import IMAGE_TOKEN_INDEX
 
 EXTRA_PROMPT = ("The video captures 3D spatial information of a scene. Please focus on the spatial relationships in the video and "
@@ -165,7 +166,7 @@ def default_workers():
 
 def model_answer_fn(model, tokenizer, image_processor, video_processor, model_name, max_frame_num=32, max_new_tokens=512,
                     reuse_scenes=False, times=None, pipeline=True, group_size=16, workers=None, stats=None, record_fn=None, pool=None,
-                    box_input_fn=None, skip_fn=None, num_beams=1, length_penalty=1.0, sampling=None, stream_fn=None, processors=None):
+                    box_input_fn=None, skip_fn=None, rule=None, stream_fn=None):
     """The per-rank loop of model_scanqa.py:130-206 around `model` (the loader-produced LlavaQwenForCausalLM).
     reuse_scenes: one scene prefill per run of consecutive questions about a scene (pipelined or, with pipeline=False, synchronous).
     pipeline (default): v3d.pipeline - asynchronous host loader, prefill / grouped-decode overlap, device-side stop test; the
@@ -175,25 +176,21 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
     workers = 0 decodes on the calling thread.
     box_input_fn(line) -> [x, y, z] or None: the Scan2Cap prompt's box centre (model_scan2cap.py:137-139, 170; its PE is added to the
     <coord> token rows); skip_fn(line) -> True: the question is not run and its answer is "" (:199-200).
-    num_beams > 1 (the drivers' --num_beams; length_penalty with it): beam search per question - the plain one-question loop calling
-    model.generate_beam, or with reuse_scenes one scene prefill and Engine.answer(num_beams=N) per question.  The pipeline's cross-scene
-    decode group and answer_group's batches are greedy and are not used with beams.
-    sampling = dict(temperature, top_k, top_p, seed) (the drivers' --temperature > 0): every token is drawn by the device sampler -
-    model.generate_sample per question, or with reuse_scenes one scene prefill and Engine.answer_group(do_sample=True) per batch.
-    stream_fn(line) -> the question's sampling stream id (its index in the question file), so a record does not depend on batching,
-    on reuse_scenes or on the number of ranks.  Not with num_beams > 1.
-    processors = dict(repetition_penalty, no_repeat_ngram_size, min_new_tokens) holding the controls that are on (the drivers'
-    --repetition_penalty / --no_repeat_ngram_size / --min_new_tokens): the device logits processors on every path, greedy or sampled -
-    a row's history is its own generated tokens whatever it is batched with; the paths' raw logits still differ in their last bits (the
-    one-row and the row kernels sum in another order), so records agree between batchings and reuse_scenes up to near-ties of the
-    processed logits, as the greedy records do.  Where a long prompt cuts max_new_tokens to the engine's room, min_new_tokens is cut with
-    it (fit_processors).  Not with num_beams > 1.
+    rule: the run's v3d.generation.GenerationRule (the drivers' flags: generation.rule_from_flags; None: plain greedy).
+    num_beams > 1: beam search per question - the plain one-question loop calling model.generate_beam, or with reuse_scenes one scene
+    prefill and Engine.answer per question.  The pipeline's cross-scene decode group and answer_group's batches are greedy and are not
+    used with beams.
+    do_sample (the drivers' --temperature > 0): every token is drawn by the device sampler - model.generate_sample per question, or with
+    reuse_scenes one scene prefill and Engine.answer_group per batch.  stream_fn(line) -> the question's sampling stream id (its index
+    in the question file; it belongs to the question, not to the rule), so a record does not depend on batching, on reuse_scenes or on
+    the number of ranks.
+    The logits processors run on every path, greedy or sampled - a row's history is its own generated tokens whatever it is batched
+    with; the paths' raw logits still differ in their last bits (the one-row and the row kernels sum in another order), so records
+    agree between batchings and reuse_scenes up to near-ties of the processed logits, as the greedy records do.  Where a long prompt
+    cuts max_new_tokens to the engine's room, min_new_tokens is cut with it (GenerationRule.fit).
     They are passed to the model explicitly, so a run without the flags ignores generation_config's, as it always has."""
-    proc = dict(processors or {})
-    if proc and num_beams > 1:
-        raise ValueError("repetition_penalty / no_repeat_ngram_size / min_new_tokens cannot be combined with num_beams > 1: processors under beams are not built")
-    if sampling and num_beams > 1:
-        raise ValueError("sampling (temperature > 0) cannot be combined with num_beams > 1: beam-sample is not built")
+    rule = rule or GenerationRule()
+    sampling, proc = rule.do_sample, rule.processors
     if sampling and stream_fn is None:
         raise ValueError("sampling needs stream_fn: each question's stream id (its index in the question file)")
     record_fn = record_fn or (lambda line, text: make_record(line, text, model_name))
@@ -221,10 +218,11 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
                 with torch.inference_mode():
                     if sampling:
                         toks = model.generate_sample(ids, images=images, modalities="video", num_beams=1, max_new_tokens=max_new_tokens,
-                                                     use_cache=True, video_dict=vd, stream=stream_fn(line), processors=proc, **sampling)
-                    elif num_beams > 1:
+                                                     use_cache=True, video_dict=vd, stream=stream_fn(line), processors=proc,
+                                                     temperature=rule.temperature, top_k=rule.top_k, top_p=rule.top_p, seed=rule.seed)
+                    elif rule.num_beams > 1:
                         toks = model.generate_beam(ids, images=images, modalities="video", do_sample=False, temperature=0.0, top_p=None,
-                                                   num_beams=num_beams, length_penalty=length_penalty, max_new_tokens=max_new_tokens,
+                                                   num_beams=rule.num_beams, length_penalty=rule.length_penalty, max_new_tokens=max_new_tokens,
                                                    use_cache=True, video_dict=vd, processors=proc)
                     else:
                         toks = model.generate(ids, images=images, modalities="video", do_sample=False, temperature=0.0, top_p=None, num_beams=1,
@@ -266,14 +264,13 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
                     qs = [x[at + 1:] for x in ids[b - i: min(j, b + nb) - i]]
                     room = eng.cfg.llm.max_pos - P - max(len(q) for q in qs) + 1
                     boxes, coord_id = _boxes(lines[b: b + len(qs)])
-                    if num_beams > 1:                    # beams: one question at a time behind the scene's prefix
-                        out += [decode(eng.answer(q, max_new_tokens=min(max_new_tokens, eng.cfg.llm.max_pos - P - len(q) + 1), eos_token_id=eos,
-                                                  num_beams=num_beams, length_penalty=length_penalty,
+                    if rule.num_beams > 1:               # beams: one question at a time behind the scene's prefix
+                        out += [decode(eng.answer(q, max_new_tokens=min(max_new_tokens, eng.cfg.llm.max_pos - P - len(q) + 1), eos_token_id=eos, rule=rule,
                                                   box_input=None if boxes is None else boxes[k], coord_token_id=coord_id)) for k, q in enumerate(qs)]
                         continue
-                    draw = dict(do_sample=True, streams=[stream_fn(l) for l in lines[b: b + len(qs)]], **sampling) if sampling else {}
+                    streams = [stream_fn(l) for l in lines[b: b + len(qs)]] if sampling else None
                     answers = eng.answer_group(qs, max_new_tokens=min(max_new_tokens, room), eos_token_id=eos, box_inputs=boxes,
-                                               coord_token_id=coord_id, **draw, **fit_processors(proc, min(max_new_tokens, room)))
+                                               coord_token_id=coord_id, streams=streams, rule=rule.fit(min(max_new_tokens, room)))
                     out += [decode(a) for a in answers]
             i = j
         return out
@@ -315,7 +312,7 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
         room = eng.cfg.llm.max_pos - (max((len(p) for p in prompts), default=1) - 1 + n_vis) + 1
         t0 = time.time()
         try:
-            toks = pipe.run(samples(), min(max_new_tokens, room), eos_token_id=model._eos(), processors=proc or None)
+            toks = pipe.run(samples(), min(max_new_tokens, room), eos_token_id=model._eos(), rule=rule)
         finally:
             loader.close()
         if times is not None and lines:
@@ -367,7 +364,7 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
 
         t0 = time.time()
         try:
-            answers = pipe.run(scenes(), max_new_tokens, eos_token_id=model._eos(), processors=proc or None)
+            answers = pipe.run(scenes(), max_new_tokens, eos_token_id=model._eos(), rule=rule)
         finally:
             loader.close()
         if times is not None and lines:
@@ -378,7 +375,7 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
                           "wall_seconds": time.time() - t0})
         return [decode(t) for scene_answers in answers for t in scene_answers]
 
-    if num_beams > 1 or sampling:
+    if rule.num_beams > 1 or sampling:
         return scene_batches if reuse_scenes else one_by_one
     if reuse_scenes:
         return scene_pipelined if pipeline else scene_batches
@@ -388,65 +385,10 @@ def model_answer_fn(model, tokenizer, image_processor, video_processor, model_na
 LLM_WEIGHTS = ("bf16", "fp8", "fp4")
 
 
-def add_sampling_arguments(ap):
-    ap.add_argument("--temperature", type=float, default=0.0,
-                    help="the reference drivers' flag: 0 (default) decodes greedily; > 0 draws every token on the device from softmax(logits / "
-                         "temperature) after --top_k and --top_p (do_sample = temperature > 0).  Each question draws from its own random stream, "
-                         "numbered by its index in the question file, so the records do not depend on batching, --reuse-scenes or the number "
-                         "of ranks; sampling runs one question (or, with --reuse-scenes, one scene's batch) at a time")
-    ap.add_argument("--top_p", type=float, default=1.0, help="sampling: keep the most probable tokens whose mass before them is below top_p (1: off)")
-    ap.add_argument("--top_k", type=int, default=0, help="sampling: keep the top_k most probable tokens (0: off)")
-    ap.add_argument("--seed", type=int, default=0, help="sampling: the 64-bit seed of the run")
-
-
-def sampling_arguments(ap, a, questions=None):
-    """(sampling, stream_fn) of model_answer_fn from the parsed flags: (None, None) at temperature 0."""
-    if a.temperature < 0 or not 0.0 < a.top_p <= 1.0 or a.top_k < 0:
-        ap.error("--temperature >= 0, 0 < --top_p <= 1, --top_k >= 0")
-    if a.temperature == 0:
-        return None, None
-    if a.num_beams > 1:
-        ap.error("--temperature > 0 cannot be combined with --num_beams > 1: beam-sample is not built")
-    index = {id(q): i for i, q in enumerate(questions or [])}
-    return dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.seed), (lambda line: index[id(line)])
-
-
-def fit_processors(processors, max_new_tokens):
-    """processors with min_new_tokens bounded by the max_new_tokens a call actually runs (the runners cut it to the engine's room)"""
-    if processors and processors.get("min_new_tokens", 0) > max_new_tokens:
-        return dict(processors, min_new_tokens=max(int(max_new_tokens), 0))
-    return processors
-
-
-def add_processor_arguments(ap):
-    ap.add_argument("--repetition_penalty", type=float, default=1.0,
-                    help="the logits of every token generated so far are divided (positive) or multiplied (negative) by this (transformers' "
-                         "repetition_penalty; 1: off)")
-    ap.add_argument("--no_repeat_ngram_size", type=int, default=0,
-                    help="no n-gram of this size occurs twice in an answer (the reference drivers' commented-out no_repeat_ngram_size=3; 0: off)")
-    ap.add_argument("--min_new_tokens", type=int, default=0, help="the EOS ids cannot be chosen before this many tokens (0: off)")
-
-
-def processor_arguments(ap, a):
-    """`processors` of model_answer_fn from the parsed flags: the controls that are on ({} when none is)."""
-    if not a.repetition_penalty > 0 or a.repetition_penalty == float("inf") or a.no_repeat_ngram_size < 0 or a.min_new_tokens < 0:
-        ap.error("--repetition_penalty > 0, --no_repeat_ngram_size >= 0, --min_new_tokens >= 0")
-    if a.min_new_tokens > a.max_new_tokens:
-        ap.error("--min_new_tokens exceeds --max-new-tokens")
-    proc = {k: v for k, v, off in (("repetition_penalty", a.repetition_penalty, 1.0), ("no_repeat_ngram_size", a.no_repeat_ngram_size, 0),
-                                   ("min_new_tokens", a.min_new_tokens, 0)) if v != off}
-    if proc and a.num_beams > 1:
-        ap.error("--repetition_penalty / --no_repeat_ngram_size / --min_new_tokens cannot be combined with --num_beams > 1: transformers applies them "
-                 "to the log-softmax scores inside its beam search and a beam's history follows its parent - not built")
-    return proc
-
-
-def add_beam_arguments(ap):
-    ap.add_argument("--num_beams", type=int, default=1,
-                    help="the reference drivers' flag (model_scanqa.py:173-185): beams per question for the generation tasks; N > 1 runs one question "
-                         "at a time (with --reuse-scenes: one scene prefill, then one beam search per question) - the cross-scene decode group "
-                         "is greedy and is not used with beams")
-    ap.add_argument("--length_penalty", type=float, default=1.0, help="beam search: a finished hypothesis scores sum(log p) / n ** length_penalty")
+def question_streams(questions):
+    """stream_fn of model_answer_fn: a question's sampling stream id is its index in the question file"""
+    index = {id(q): i for i, q in enumerate(questions)}
+    return lambda line: index[id(line)]
 
 
 def load_model(model_path, overwrite_cfg=False, llm_weights="bf16", lora_path=None):
@@ -499,12 +441,9 @@ def main(argv=None):
                     help="a LoRA adapter directory (adapter_config.json, adapter_model.bin, non_lora_trainables.bin) merged into the decoder at load")
     ap.add_argument("--n_gpu", type=int, default=None,
                     help="the reference's flag (model_scanqa.py:222): started plainly with N > 1, launch N ranks of this runner on this node")
-    add_beam_arguments(ap)
-    add_sampling_arguments(ap)
-    add_processor_arguments(ap)
+    add_arguments(ap)
     a = ap.parse_args(argv)
-    sampling_arguments(ap, a)
-    processors = processor_arguments(ap, a)
+    rule = rule_from_flags(ap, a)
     if os.path.exists(a.answer_file):                                                         # model_scanqa.py:238-240
         print(f"The {a.answer_file} already exists!!!")
         return 0
@@ -514,8 +453,7 @@ def main(argv=None):
     with open(os.path.expanduser(a.question_file)) as f:
         questions = json.load(f)[: a.test_size]
     pool = None
-    sampling, stream_fn = sampling_arguments(ap, a, questions)
-    if not a.no_pipeline and a.loader_workers >= 0 and a.num_beams == 1 and not sampling:
+    if not a.no_pipeline and a.loader_workers >= 0 and rule.num_beams == 1 and not rule.do_sample:
         from . import frame_io
         pool = frame_io.make_pool(a.loader_workers or default_workers())        # forked before this process touches the GPU
     rank, world, dev, gather_dev = rank_setup(a.n_gpu)
@@ -527,7 +465,7 @@ def main(argv=None):
     times = []
     fn = model_answer_fn(model, tokenizer, image_processor, vp, name, a.max_frame_num, a.max_new_tokens, a.reuse_scenes, times,
                          pipeline=not a.no_pipeline, group_size=a.decode_group, workers=(0 if a.loader_workers < 0 else a.loader_workers or None), pool=pool,
-                         num_beams=a.num_beams, length_penalty=a.length_penalty, sampling=sampling, stream_fn=stream_fn, processors=processors)
+                         rule=rule, stream_fn=question_streams(questions))
     records = evaluate(questions, fn, rank, world, gather_dev, shard=a.shard or ("scene" if a.reuse_scenes else "stride"))
     if rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(a.answer_file)), exist_ok=True)

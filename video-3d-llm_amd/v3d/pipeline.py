@@ -24,6 +24,15 @@ import torch
 
 from . import ops
 from ._native import V3DError
+from .generation import GenerationRule
+
+
+def _greedy_rule(rule):
+    """The rule of a pipeline run (None: plain greedy): the groups choose greedily, so the logits processors are what it may turn on."""
+    rule = rule or GenerationRule()
+    if rule.num_beams > 1 or rule.do_sample or rule.return_logits:
+        raise V3DError("the pipelines decode greedily in groups: beams, sampling and return_logits run one question or one scene's batch at a time")
+    return rule
 
 
 @dataclass
@@ -292,15 +301,13 @@ class ScenePipeline:
 
     # ------------------------------------------------------------------ the whole list
     @torch.no_grad()
-    def run(self, samples, max_new_tokens, eos_token_id=None, overlap=True, stamps=None, trim=True, processors=None):
+    def run(self, samples, max_new_tokens, eos_token_id=None, overlap=True, stamps=None, trim=True, rule=None):
         """samples: iterable of SceneSample (consumed lazily, one decode group ahead).  Returns one host LongTensor of new token ids
         per sample, in order, cut after its first EOS (trim=False: the untrimmed [n, steps] rows per group, for benchmarking).
-        processors: dict(repetition_penalty, no_repeat_ngram_size, min_new_tokens) or None - Engine._processors, handed to every group's
-        decode (all rows of a group start at step 0, so a row's history is its column of the group's token buffer)."""
+        rule: a v3d.generation.GenerationRule or None (_greedy_rule); its Engine._choice is handed to every group's decode (all rows of
+        a group start at step 0, so a row's history is its column of the group's token buffer)."""
         eng, G = self.eng, self.G
-        if processors and processors.get("min_new_tokens", 0) > max_new_tokens:          # the caller cut max_new_tokens to the engine's room
-            processors = dict(processors, min_new_tokens=max_new_tokens)
-        proc = eng._processors(eos=eos_token_id, max_new_tokens=max_new_tokens, **processors) if processors else None
+        choice = eng._choice(_greedy_rule(rule).fit(max_new_tokens), eos_token_id, max_new_tokens)      # (the caller cut max_new_tokens to the engine's room)
         sA, sB = self.streams
         it = iter(samples)
         keep = eng.ctx
@@ -349,7 +356,7 @@ class ScenePipeline:
                 with torch.cuda.stream(sB if overlap else torch.cuda.current_stream()):
                     for ev in pre_done:
                         torch.cuda.current_stream().wait_event(ev)
-                    toks = eng.decode_group(self.groups[gi % 2], ctxs, lens, max_new_tokens, eos_token_id=eos_token_id, processors=proc)
+                    toks = eng.decode_group(self.groups[gi % 2], ctxs, lens, max_new_tokens, eos_token_id=eos_token_id, choice=choice)
                     out += eng.trim_at_eos(toks, eos_token_id) if trim else [toks.cpu()]
                 gi += 1
             if overlap:
@@ -389,12 +396,13 @@ class SceneReusePipeline:
         return self.inputs.upload_seconds
 
     @torch.no_grad()
-    def run(self, scenes, max_new_tokens, eos_token_id=None, overlap=True, processors=None):
+    def run(self, scenes, max_new_tokens, eos_token_id=None, overlap=True, rule=None):
         """scenes: iterable of (SceneSample whose input_ids are the PREFIX ids up to and including <image>, [question id tensors] or a
         SceneJob) - consumed lazily, one scene ahead.  Returns, per scene, the list of its answers' token-id tensors (host, cut after the
         first EOS) or, for a grounding job, of its queries' score vectors (host).  A scene without questions is prefilled and gives [].
-        processors: dict(repetition_penalty, no_repeat_ngram_size, min_new_tokens) or None, handed to every answer_group call."""
+        rule: a v3d.generation.GenerationRule or None (plain greedy), handed to every answer_group call."""
         eng = self.eng
+        rule = _greedy_rule(rule)
         keep_ctx, keep_ws = eng.ctx, eng.ws
         it = iter(scenes)
         cur = torch.cuda.current_stream()
@@ -441,14 +449,11 @@ class SceneReusePipeline:
                         if job.ground_rows is not None:
                             answers += list(eng.ground_group(qs, job.ground_rows[b0: b0 + self.batch]).cpu())
                             continue
-                        room = eng.cfg.llm.max_pos - P - max(int(q.numel()) for q in qs) + 1
-                        proc = dict(processors or {})
-                        if proc.get("min_new_tokens", 0) > min(max_new_tokens, room):         # cut with max_new_tokens
-                            proc["min_new_tokens"] = max(min(max_new_tokens, room), 0)
+                        n_new = min(max_new_tokens, eng.cfg.llm.max_pos - P - max(int(q.numel()) for q in qs) + 1)
                         answers += [a.cpu() for a in eng.answer_group(
-                            qs, max_new_tokens=min(max_new_tokens, room), eos_token_id=eos_token_id,
+                            qs, max_new_tokens=n_new, eos_token_id=eos_token_id,
                             box_inputs=None if job.box_inputs is None else job.box_inputs[b0: b0 + self.batch],
-                            coord_token_id=job.coord_token_id, **proc)]
+                            coord_token_id=job.coord_token_id, rule=rule.fit(n_new))]
                     read[k % 2] = sB.record_event()
                 out.append(answers)
             if overlap:
