@@ -271,7 +271,9 @@ int v3d_gemm_layout(const void* A, int64_t lda, int a_kmajor, const void* B, int
 /* FP8 (OCP e4m3) variant of the LLM linears - BASELINE configs[3]; not part of the reference (tolerance is
  * re-stated in tests/test_gpu_fp8.py).  y[m,n] = sa[m] * sw[n] * sum_k qa[m,k] qw[n,k] with per-row scales.
  * v3d_quantize_fp8_rows: x [rows, cols] (f16/bf16) -> q [rows, cols] e4m3 bytes (row stride ldq) + scale[rows] f32,
- *   scale = amax|row| / 448.  Used for activations per call and for weights once at load.
+ *   scale = amax|row| / 448 in f32, floored at the smallest normal f32 (2^-126) so that 1 / scale stays finite for rows of
+ *   subnormal size; an all-zero row gets scale 1 and zero bytes.  q = e4m3(x * (1 / scale)), round to nearest even.  Used for
+ *   activations per call and for weights once at load.
  * v3d_gemm_fp8: A [M,K] e4m3 (lda bytes), W [N,K] e4m3; N % 256 == 0, K % 128 == 0; epilogues NONE / BIAS / RES /
  *   SWIGLU (same codes and row interleave as v3d_gemm); output in out_dtype (f16 / bf16). */
 int v3d_quantize_fp8_rows(const void* x, int64_t ldx, int64_t rows, int cols, int dtype, void* q, int64_t ldq,

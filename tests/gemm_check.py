@@ -108,12 +108,14 @@ def n_out(N, epi):
     return N // 2 if epi == EPI_SWIGLU else N
 
 
-def reference(a, w, bias=None, res=None, epi=EPI_NONE, res_mod=0, rows=None, lin_rel=0.0):
+def reference(a, w, bias=None, res=None, epi=EPI_NONE, res_mod=0, rows=None, lin_rel=0.0, dt=None, depth=None):
     """The rows `rows` (a slice, default all) of epilogue(a w^T) -> dict of f64 [R, n_out]: out, bound, rounded, and for the GELUs and
     SwiGLU lo / hi (the interval a kernel must hit when yr is exact).  ymax = max |y| (linear output) of these rows.
     lin_rel (0 for v3d_gemm): a further relative f32 rounding of the linear output, lin += lin_rel |y| (tests/decode_check.py: the e4m3
-    decode rows multiply the f32 sum by the row scale once, 2^-24 |y|); w may be given in f64 (dequantised weights)."""
-    dt = a.dtype
+    decode rows multiply the f32 sum by the row scale once, 2^-24 |y|); w may be given in f64 (dequantised weights).
+    dt, depth (tests/qgemm_check.py): the output type where a is given in f64 too (dequantised activations), and the depth of the
+    summation chain where it is not K / 32 + C0."""
+    dt = dt or a.dtype
     h = H[dt]
     tiny = TINY if dt == torch.float16 else 0.0
     M, K = a.shape
@@ -126,7 +128,7 @@ def reference(a, w, bias=None, res=None, epi=EPI_NONE, res_mod=0, rows=None, lin
     if epi in HAS_BIAS:
         y = y + bias.double()
         mag = mag + bias.double().abs()
-    lin = C_ACC * (K / 32.0 + C0) * 2.0 ** -24 * mag + (h + lin_rel) * y.abs() + tiny
+    lin = C_ACC * (depth or K / 32.0 + C0) * 2.0 ** -24 * mag + (h + lin_rel) * y.abs() + tiny
     del mag
     ymax = y.abs().max().item()
     if dt == torch.float16:
@@ -165,7 +167,7 @@ def reference(a, w, bias=None, res=None, epi=EPI_NONE, res_mod=0, rows=None, lin
     return o
 
 
-def compare(got, a, w, bias=None, res=None, epi=EPI_NONE, res_mod=0, exact=False, block=2048, lin_rel=0.0):
+def compare(got, a, w, bias=None, res=None, epi=EPI_NONE, res_mod=0, exact=False, block=2048, lin_rel=0.0, dt=None, depth=None):
     """Every element of got [M, n_out] against the reference, in row blocks -> dict:
     ratio     worst |got - out| / bound (inf if any element is not finite: never written, or NaN)
     unequal   elements that differ from `rounded`;  outside: elements outside [lo, hi] (GELUs, SwiGLU; = unequal for the others)
@@ -176,7 +178,7 @@ def compare(got, a, w, bias=None, res=None, epi=EPI_NONE, res_mod=0, exact=False
     worst, unequal, outside, ymax, need = 0.0, 0, 0, 0.0, 0
     for r0 in range(0, M, block):
         rows = slice(r0, min(M, r0 + block))
-        ref = reference(a, w, bias, res, epi, res_mod, rows, lin_rel)
+        ref = reference(a, w, bias, res, epi, res_mod, rows, lin_rel, dt, depth)
         g = got[rows].to(ref["out"].device).double()
         if not bool(torch.isfinite(g).all()):
             worst = float("inf")
@@ -188,8 +190,8 @@ def compare(got, a, w, bias=None, res=None, epi=EPI_NONE, res_mod=0, exact=False
         ymax = max(ymax, ref["ymax"])
         if exact:
             y = a[rows].double() @ w.double().T + (bias.double() if epi in HAS_BIAS else 0.0)
-            need += int((rnd(y, a.dtype) != y).sum())
-    if exact and a.dtype == torch.float16:
+            need += int((rnd(y, dt or a.dtype) != y).sum())
+    if exact and (dt or a.dtype) == torch.float16:
         assert ymax < 60000.0, f"exact f16 case too large: max |y| = {ymax}"
     return {"ratio": worst, "unequal": unequal, "outside": outside, "ymax": ymax, "needs_rounding": need / float(M * N)}
 

@@ -17,8 +17,10 @@ namespace v3d {
 template <typename T, int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_fp8_kernel(Q8GemmArgs p) { q8_gemm_tile<T, EPI, WfE4m3>(p); }
 
-// The e4m3 quantisers share: scale = amax / 448 (1 if the row is zero), and 8 values times 1 / scale packed into 8 saturated bytes.
-__device__ __forceinline__ float e4m3_row_scale(float amax) { return amax > 0.f ? amax / 448.0f : 1.0f; }
+// The e4m3 quantisers share: scale = amax / 448, floored at the smallest normal f32 (1 if the row is zero), and 8 values times
+// 1 / scale packed into 8 saturated bytes.  The floor keeps 1 / scale finite: below amax = 448 * 2^-126 the quotient is an f32
+// subnormal, its reciprocal inf, and the zeros of such a row would become 0 * inf = the NaN byte.
+__device__ __forceinline__ float e4m3_row_scale(float amax) { return amax > 0.f ? fmaxf(amax / 448.0f, 1.17549435e-38f) : 1.0f; }
 
 template <class F>
 __device__ __forceinline__ uint2 e4m3_pack8(F at, float inv) {      // at(j) = the j-th value
@@ -30,7 +32,7 @@ __device__ __forceinline__ uint2 e4m3_pack8(F at, float inv) {      // at(j) = t
   return make_uint2((uint32_t)w0, (uint32_t)w1);
 }
 
-// Row-wise e4m3 quantisation: scale[r] = amax|x[r,:]| / 448 (1 if the row is zero), q = sat_e4m3(x / scale).
+// Row-wise e4m3 quantisation: scale[r] = max(amax|x[r,:]| / 448, 2^-126) (1 if the row is zero), q = sat_e4m3(x / scale).
 // One wave per row, two passes over the row (second pass from L2).
 template <typename T>
 __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const T* __restrict__ x, int64_t ldx, int64_t rows, int cols,
