@@ -7,24 +7,11 @@
 //                       non-temporal 16-byte loads (read-once data, keep L2 for the activations);
 //                       epilogues: bias / residual / SwiGLU over tile-interleaved gate|up rows.
 //   v3d_rope_kv_append: rotary on the new q and k heads + copy of k,v into the cache row, one launch.
-#include "v3d_common.h"
+#include "decode_common.h"
 #include <mutex>
 #include <unordered_map>
 
 namespace v3d {
-
-enum { DEC_EPI_NONE = 0, DEC_EPI_BIAS = 1, DEC_EPI_RES = 2, DEC_EPI_SWIGLU = 3 };
-
-__device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
-
-__device__ __forceinline__ uint4 ldg_nt(const uint4* p) {
-  uint4 r;
-  r.x = __builtin_nontemporal_load(&p->x);
-  r.y = __builtin_nontemporal_load(&p->y);
-  r.z = __builtin_nontemporal_load(&p->z);
-  r.w = __builtin_nontemporal_load(&p->w);
-  return r;
-}
 
 // Workgroup = 4 waves = FOUR weight rows; the K range is split over the 256 threads (chunk k = tid + 256 i), so
 // every row is streamed by all four waves at once: N/4 workgroups (1152 for the QKV linear) keep the whole chip
@@ -42,16 +29,7 @@ __global__ __launch_bounds__(256, M == 1 ? 8 : 4) void linear_decode_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int kv = K / 8;
   int rows[4];
-  int o0;
-  if (EPI == DEC_EPI_SWIGLU) {
-    o0 = blockIdx.x * 2;                                   // two outputs = two (gate, up) row pairs
-    rows[0] = (o0 >> 6) * 128 + (o0 & 63); rows[1] = rows[0] + 64;
-    rows[2] = ((o0 + 1) >> 6) * 128 + ((o0 + 1) & 63); rows[3] = rows[2] + 64;
-  } else {
-    o0 = blockIdx.x * 4;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) rows[r] = o0 + r;
-  }
+  const int o0 = dec_valu_rows<EPI>(rows);
   uint4 xn[M][2];
   if (NORM) {                                              // kv <= 512: chunks tid and tid + 256
     float ss[M];
@@ -128,36 +106,7 @@ __global__ __launch_bounds__(256, M == 1 ? 8 : 4) void linear_decode_kernel(
       for (int m = 0; m < M; ++m) fma8(m, reinterpret_cast<const uint4*>(x + m * ldx)[k], a, b, c, d);
     }
   }
-#pragma unroll
-  for (int m = 0; m < M; ++m)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) s[m][r] += __shfl_xor(s[m][r], off);
-    }
-  if (lane == 0) {
-#pragma unroll
-    for (int m = 0; m < M; ++m)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) red[m][r][wave] = s[m][r];
-  }
-  __syncthreads();
-  if (EPI == DEC_EPI_SWIGLU) {
-    if (tid < 2 * M) {
-      const int m = tid >> 1, t2 = tid & 1;
-      const float g = round_to<T>(red[m][2 * t2][0] + red[m][2 * t2][1] + red[m][2 * t2][2] + red[m][2 * t2][3]);
-      const float u = round_to<T>(red[m][2 * t2 + 1][0] + red[m][2 * t2 + 1][1] + red[m][2 * t2 + 1][2] + red[m][2 * t2 + 1][3]);
-      out[m * ldo + o0 + t2] = from_f32<T>(round_to<T>(silu_f(g)) * u);
-    }
-  } else if (tid < 4 * M) {
-    const int m = tid >> 2, r = tid & 3;
-    const int n = o0 + r;
-    float v = red[m][r][0] + red[m][r][1] + red[m][r][2] + red[m][r][3];
-    if (EPI == DEC_EPI_BIAS) v += to_f32(bias[n]);
-    v = round_to<T>(v);                                   // the linear's own output rounding
-    if (EPI == DEC_EPI_RES) v += to_f32(res[m * ldr + n]);
-    out[m * ldo + n] = from_f32<T>(v);
-  }
+  dec_valu_tail<T, EPI, M, false>(s, red, rows, o0, nullptr, DecStore<T, EPI>{bias, res, ldr, out, ldo});
 }
 
 // Matrix-core form of the decode linear for up to 16 activation rows (scenes decoding together): the weights are the
@@ -170,16 +119,6 @@ __global__ __launch_bounds__(256, M == 1 ? 8 : 4) void linear_decode_kernel(
 // back; two tiles of loads stay in flight in registers.  No workgroup barrier in the loop: the tile is wave-private and
 // the LDS pipeline keeps a wave's writes and reads in order.  Partial 16 x 16 tiles meet in LDS at the end.  Column m of
 // the result depends on row m of x only, so a scene's numbers do not depend on its group.
-using dec_f32x4 = __attribute__((ext_vector_type(4))) float;
-using dec_bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using dec_f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-__device__ __forceinline__ dec_f32x4 dec_mfma(bf16_t, const uint4& a, const uint4& b, dec_f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(dec_bf16x8, a), __builtin_bit_cast(dec_bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ dec_f32x4 dec_mfma(f16_t, const uint4& a, const uint4& b, dec_f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(dec_f16x8, a), __builtin_bit_cast(dec_f16x8, b), c, 0, 0, 0);
-}
-
 // MB (r04): 16-row blocks of activation rows - M <= 16 MB scenes / questions share the pass over the weights (a weight fragment feeds MB
 // MFMAs; the accumulators of the blocks are independent, so a row's bits depend neither on M nor on MB).
 // OG (r04): 16-row groups of OUTPUTS per workgroup.  Every workgroup reads all M activation rows (each wave its K slices), so the
@@ -189,7 +128,7 @@ template <typename T, int EPI, int MB, int OG>
 __global__ __launch_bounds__(512) void linear_decode_mfma_kernel(const T* __restrict__ x, int64_t ldx, int M, const T* __restrict__ W,
                                                                  int64_t ldw, const T* __restrict__ bias, const T* __restrict__ res,
                                                                  int64_t ldr, T* __restrict__ out, int64_t ldo, int N, int K) {
-  constexpr int SW = EPI == DEC_EPI_SWIGLU ? 2 : 1;         // weight row groups per output group (gate + up)
+  constexpr int SW = EPI == V3D_DEC_SWIGLU ? 2 : 1;         // weight row groups per output group (gate + up)
   constexpr int RG = SW * OG;                               // 16-row weight groups per workgroup: [og][gate | up]
   constexpr int UN = RG * MB >= 8 ? 1 : 2;                  // 128-element K tiles in flight per wave (8 x 16 B of weights per lane and group)
   constexpr int PITCH = 272;                                // LDS row pitch in bytes (256 + 16)
@@ -203,23 +142,12 @@ __global__ __launch_bounds__(512) void linear_decode_mfma_kernel(const T* __rest
   const int o0 = blockIdx.x * 16 * OG;                      // first output of this workgroup
   const T* wbase[RG];                                       // row lr of the group, chunk lc
 #pragma unroll
-  for (int og = 0; og < OG; ++og) {
-    const int o = o0 + 16 * og;
-    if (EPI == DEC_EPI_SWIGLU) {
-      const int gate = (o >> 6) * 128 + (o & 63);           // tile-interleaved rows: 64 gate rows, then their 64 up rows
-      wbase[SW * og] = W + (int64_t)(gate + lr) * ldw + 8 * lc;
-      wbase[SW * og + SW - 1] = W + (int64_t)(gate + 64 + lr) * ldw + 8 * lc;
-    } else {
-      wbase[SW * og] = W + (int64_t)(o + lr) * ldw + 8 * lc;
-    }
-  }
+  for (int og = 0; og < OG; ++og)
+#pragma unroll
+    for (int q = 0; q < SW; ++q) wbase[SW * og + q] = W + (int64_t)(dec_row0<EPI>(o0 + 16 * og) + 64 * q + lr) * ldw + 8 * lc;
   bool col_ok[MB];
   const T* xrow[MB];
-#pragma unroll
-  for (int b = 0; b < MB; ++b) {
-    col_ok[b] = r + 16 * b < M;
-    xrow[b] = x + (int64_t)(col_ok[b] ? r + 16 * b : 0) * ldx + 8 * g;
-  }
+  dec_x_rows(x, ldx, M, r, 8 * g, col_ok, xrow);
   dec_f32x4 acc[RG][MB];
 #pragma unroll
   for (int q = 0; q < RG; ++q)
@@ -265,38 +193,7 @@ __global__ __launch_bounds__(512) void linear_decode_mfma_kernel(const T* __rest
     }
   }
   __syncthreads();                                          // the partial sums reuse the tiles' LDS
-#pragma unroll
-  for (int q = 0; q < RG; ++q)
-#pragma unroll
-    for (int b = 0; b < MB; ++b)
-      *reinterpret_cast<float4*>(part(wave, q, b) + lane * 4) = make_float4(acc[q][b][0], acc[q][b][1], acc[q][b][2], acc[q][b][3]);
-  __syncthreads();
-  for (int e = tid; e < 256 * MB * OG; e += 512) {          // element (row 4 (l >> 4) + i, column l & 15) of block b, group og
-    const int og = e / (256 * MB), e2 = e - og * 256 * MB;
-    const int b = e2 >> 8, t8 = e2 & 255;
-    const int l = t8 >> 2, i = t8 & 3;
-    const int row = 4 * (l >> 4) + i, m = (l & 15) + 16 * b;
-    float v[SW];
-#pragma unroll
-    for (int q = 0; q < SW; ++q) {
-      v[q] = 0.f;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) v[q] += part(w, SW * og + q, b)[t8];
-    }
-    if (m < M) {
-      const int n = o0 + 16 * og + row;
-      if (EPI == DEC_EPI_SWIGLU) {
-        const float gt = round_to<T>(v[0]), up = round_to<T>(v[SW - 1]);
-        out[m * ldo + n] = from_f32<T>(round_to<T>(silu_f(gt)) * up);
-      } else {
-        float y = v[0];
-        if (EPI == DEC_EPI_BIAS) y += to_f32(bias[n]);
-        y = round_to<T>(y);                                 // the linear's own output rounding
-        if (EPI == DEC_EPI_RES) y += to_f32(res[m * ldr + n]);
-        out[m * ldo + n] = from_f32<T>(y);
-      }
-    }
-  }
+  dec_mfma_tail<T, EPI, MB, OG, false>(tid, lane, wave, acc, part, o0, M, nullptr, DecStore<T, EPI>{bias, res, ldr, out, ldo});
 }
 
 // ---- r04 (second session): the matrix-core decode linear as a PIPELINED stream ----------------------------------------------------
@@ -333,12 +230,6 @@ __device__ __forceinline__ void dec2_mult(const char* tl, int r, int g, const ui
   }
 }
 
-template <int EPI>
-__device__ __forceinline__ int dec2_row0(int grp) {                      // first weight row of 16-output group grp (SWIGLU: its gate rows)
-  const int o = 16 * grp;
-  return EPI == DEC_EPI_SWIGLU ? (o >> 6) * 128 + (o & 63) : o;
-}
-
 // NW = K tiles of THIS wave (the workgroup's waves hold NT or NT - 1: two instantiations of the loop, chosen once per wave)
 // NORM: x holds the rows BEFORE Qwen2RMSNorm; the workgroup forms every row's 1 / rms itself - in the summation order v3d_rmsnorm uses
 // for more than four rows (rmsnorm_kernel's; the host sends up to four rows elsewhere), so the bits are those of the separate launch - and
@@ -349,7 +240,7 @@ __device__ __forceinline__ void dec2_run(const T* __restrict__ x, int64_t ldx, i
                                          const T* __restrict__ bias, const T* __restrict__ res, int64_t ldr, T* __restrict__ out,
                                          int64_t ldo, int groups, char* smem_, float* __restrict__ partial,
                                          const T* __restrict__ norm_w = nullptr, float eps = 0.f, int cols = 0, float* nrm_lds = nullptr) {
-  constexpr int SW = EPI == DEC_EPI_SWIGLU ? 2 : 1;
+  constexpr int SW = EPI == V3D_DEC_SWIGLU ? 2 : 1;
   constexpr int PITCH = 272, TILE_B = 8 * SW * 16 * PITCH, PART_F = 8 * SW * MB * 256;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, g = lane >> 4, lr = lane >> 4, lc = lane & 15;
@@ -427,7 +318,7 @@ __device__ __forceinline__ void dec2_run(const T* __restrict__ x, int64_t ldx, i
   int iq = 0;
   auto issue = [&](uint4 (&wr)[4]) {
     const int igc = ig < my_groups ? ig : my_groups - 1;
-    const T* base = wlane + (int64_t)(dec2_row0<EPI>((int)blockIdx.x + igc * (int)gridDim.x) + 64 * iq) * ldw + 1024 * iu;
+    const T* base = wlane + (int64_t)(dec_row0<EPI>(16 * ((int)blockIdx.x + igc * (int)gridDim.x)) + 64 * iq) * ldw + 1024 * iu;
 #pragma unroll
     for (int j = 0; j < 4; ++j) wr[j] = ldg_nt(reinterpret_cast<const uint4*>(base + (int64_t)(4 * j) * ldw));
     if (++iq == SW) { iq = 0; if (++iu == NW) { iu = 0; ++ig; } }
@@ -439,47 +330,26 @@ __device__ __forceinline__ void dec2_run(const T* __restrict__ x, int64_t ldx, i
     for (int b = 0; b < MB; ++b) acc[q][b] = dec_f32x4{0.f, 0.f, 0.f, 0.f};
   // epilogue element of this thread (MB = 1: threads 0..255 only): block b, row / column of the 16 x 16 tile
   const bool epi_on = tid < 256 * MB;
-  const int eb = tid >> 8, t8 = tid & 255, el = t8 >> 2, ei = t8 & 3;
-  const int erow = 4 * (el >> 4) + ei, em = (el & 15) + 16 * eb;
+  const DecElem el = dec_elem(tid);
   auto group_end = [&](int pb, int gi, float side) {
-#pragma unroll
-    for (int q = 0; q < SW; ++q)
-#pragma unroll
-      for (int b = 0; b < MB; ++b) {
-        *reinterpret_cast<float4*>(part(pb, wave, q, b) + lane * 4) = make_float4(acc[q][b][0], acc[q][b][1], acc[q][b][2], acc[q][b][3]);
-        acc[q][b] = dec_f32x4{0.f, 0.f, 0.f, 0.f};
-      }
+    auto part_pb = [&](int w, int q, int b_) -> float* { return part(pb, w, q, b_); };
+    dec_part_put<true>(lane, wave, acc, part_pb);
     // LDS-only rendezvous: __syncthreads() is a workgroup-scope fence, i.e. s_waitcnt vmcnt(0) - it drained the weight stream every group
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     if (epi_on) {
       float v[SW];
-#pragma unroll
-      for (int q = 0; q < SW; ++q) {
-        v[q] = 0.f;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) v[q] += part(pb, w, q, eb)[t8];
-      }
-      if (em < M) {
-        const int n = 16 * ((int)blockIdx.x + gi * (int)gridDim.x) + erow;
-        if (SPLIT) {                                        // this K chunk's f32 sum: decode_combine_kernel adds the chunks in order
-          partial[(int64_t)em * (16 * groups) + n] = v[0];
-        } else if (EPI == DEC_EPI_SWIGLU) {
-          const float gt = round_to<T>(v[0]), up = round_to<T>(v[SW - 1]);
-          out[em * ldo + n] = from_f32<T>(round_to<T>(silu_f(gt)) * up);
-        } else {
-          float y = v[0];
-          if (EPI == DEC_EPI_BIAS) y += side;
-          y = round_to<T>(y);                               // the linear's own output rounding
-          if (EPI == DEC_EPI_RES) y += side;
-          out[em * ldo + n] = from_f32<T>(y);
-        }
+      dec_part_sum<SW>(part_pb, 0, el, v);
+      if (el.m < M) {
+        const int n = 16 * ((int)blockIdx.x + gi * (int)gridDim.x) + el.row;
+        if (SPLIT) partial[(int64_t)el.m * (16 * groups) + n] = v[0];   // this K chunk's f32 sum: decode_combine_kernel adds the chunks in order
+        else out[el.m * ldo + n] = dec_finish<T, EPI>(v[0], v[SW - 1], side, side);
       }
     }
   };
   auto side_load = [&](int gi) -> float {                  // requested a whole group ahead of its use; unconditional (rows beyond M read row 0)
-    const int n = 16 * ((int)blockIdx.x + gi * (int)gridDim.x) + erow;
-    if (EPI == DEC_EPI_BIAS && !SPLIT) return to_f32(bias[n]);
-    if (EPI == DEC_EPI_RES && !SPLIT) return to_f32(res[(int64_t)(em < M ? em : 0) * ldr + n]);
+    const int n = 16 * ((int)blockIdx.x + gi * (int)gridDim.x) + el.row;
+    if (EPI == V3D_DEC_BIAS && !SPLIT) return to_f32(bias[n]);
+    if (EPI == V3D_DEC_RES && !SPLIT) return to_f32(res[(int64_t)(el.m < M ? el.m : 0) * ldr + n]);
     return 0.f;
   };
   uint4 wa[4], wb[4];
@@ -519,7 +389,7 @@ __global__ __launch_bounds__(512) void linear_decode_mfma2_kernel(const T* __res
                                                                   int64_t ldw, const T* __restrict__ bias, const T* __restrict__ res,
                                                                   int64_t ldr, T* __restrict__ out, int64_t ldo, int K, int groups,
                                                                   const T* __restrict__ norm_w, float eps) {
-  constexpr int SW = EPI == DEC_EPI_SWIGLU ? 2 : 1;
+  constexpr int SW = EPI == V3D_DEC_SWIGLU ? 2 : 1;
   __shared__ __attribute__((aligned(16))) char smem_[8 * SW * 16 * 272 + 2 * 8 * SW * MB * 256 * 4];
   __shared__ float nrm_[NORM ? 48 : 1];
   const int wave = threadIdx.x >> 6;
@@ -543,8 +413,8 @@ __global__ __launch_bounds__(512) void linear_decode_mfma2_split_kernel(const T*
   x += 128 * t0;
   W += 128 * t0;
   partial += (int64_t)c * (16 * MB) * (16 * groups);
-  if (nt_w == NT) dec2_run<T, DEC_EPI_NONE, MB, NT, true>(x, ldx, M, W, ldw, nullptr, nullptr, 0, nullptr, 0, groups, smem_, partial);
-  else dec2_run<T, DEC_EPI_NONE, MB, (NT > 1 ? NT - 1 : 1), true>(x, ldx, M, W, ldw, nullptr, nullptr, 0, nullptr, 0, groups, smem_, partial);
+  if (nt_w == NT) dec2_run<T, V3D_DEC_NONE, MB, NT, true>(x, ldx, M, W, ldw, nullptr, nullptr, 0, nullptr, 0, groups, smem_, partial);
+  else dec2_run<T, V3D_DEC_NONE, MB, (NT > 1 ? NT - 1 : 1), true>(x, ldx, M, W, ldw, nullptr, nullptr, 0, nullptr, 0, groups, smem_, partial);
 }
 
 template <typename T, int EPI>
@@ -555,10 +425,7 @@ __global__ __launch_bounds__(256) void decode_combine_kernel(const float* __rest
   if (n >= N || m >= M) return;
   float y = 0.f;
   for (int c = 0; c < chunks; ++c) y += partial[((int64_t)c * rows_pad + m) * N + n];
-  if (EPI == DEC_EPI_BIAS) y += to_f32(bias[n]);
-  y = round_to<T>(y);                                       // the linear's own output rounding
-  if (EPI == DEC_EPI_RES) y += to_f32(res[m * ldr + n]);
-  out[m * ldo + n] = from_f32<T>(y);
+  DecStore<T, EPI>{bias, res, ldr, out, ldo}(y, y, m, n);
 }
 
 // any K: one 16-output group per workgroup, weights and activations of tile j + 2 in flight while tile j is multiplied
@@ -566,7 +433,7 @@ template <typename T, int EPI, int MB>
 __global__ __launch_bounds__(512) void linear_decode_mfma_stream_kernel(const T* __restrict__ x, int64_t ldx, int M, const T* __restrict__ W,
                                                                         int64_t ldw, const T* __restrict__ bias, const T* __restrict__ res,
                                                                         int64_t ldr, T* __restrict__ out, int64_t ldo, int K) {
-  constexpr int SW = EPI == DEC_EPI_SWIGLU ? 2 : 1;
+  constexpr int SW = EPI == V3D_DEC_SWIGLU ? 2 : 1;
   constexpr int PITCH = 272, TILE_B = 8 * SW * 16 * PITCH, PART_B = 8 * SW * MB * 256 * 4;
   __shared__ __attribute__((aligned(16))) char smem_[TILE_B > PART_B ? TILE_B : PART_B];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -575,14 +442,11 @@ __global__ __launch_bounds__(512) void linear_decode_mfma_stream_kernel(const T*
   auto part = [&](int w, int q, int b_) -> float* { return reinterpret_cast<float*>(smem_) + (size_t)((w * SW + q) * MB + b_) * 256; };
   const int tiles = K / 128;
   const int nt_w = tiles > wave ? (tiles - wave + 7) / 8 : 0;
-  const T* wlane = W + (int64_t)(dec2_row0<EPI>((int)blockIdx.x) + lr) * ldw + 8 * lc + 128 * wave;
+  const int o0 = 16 * (int)blockIdx.x;
+  const T* wlane = W + (int64_t)(dec_row0<EPI>(o0) + lr) * ldw + 8 * lc + 128 * wave;
   const T* xlane[MB];
   bool col_ok[MB];
-#pragma unroll
-  for (int b = 0; b < MB; ++b) {
-    col_ok[b] = r + 16 * b < M;
-    xlane[b] = x + (int64_t)(col_ok[b] ? r + 16 * b : 0) * ldx + 8 * g + 128 * wave;
-  }
+  dec_x_rows(x, ldx, M, r, 8 * g + 128 * wave, col_ok, xlane);
   dec_f32x4 acc[SW][MB];
 #pragma unroll
   for (int q = 0; q < SW; ++q)
@@ -621,17 +485,14 @@ __global__ __launch_bounds__(512) void linear_decode_mfma_stream_kernel(const T*
     issue_x(xr, u_next);
     __builtin_amdgcn_sched_barrier(0);
   };
-  const bool epi_on = tid < 256 * MB;
-  const int eb = tid >> 8, t8 = tid & 255, el = t8 >> 2, ei = t8 & 3;
-  const int erow = 4 * (el >> 4) + ei, em = (el & 15) + 16 * eb;
-  const int n = 16 * (int)blockIdx.x + erow;
+  const DecElem el = dec_elem(tid);                         // this thread's element of the tail (MB = 1: threads 0..255 only)
   uint4 wa[SW][4], wb[SW][4], xa[MB][4], xb[MB][4];
   issue_w(wa, 0); issue_x(xa, 0);
   issue_w(wb, 1); issue_x(xb, 1);
   float side = 0.f;                                         // older than every later tile request: its wait is a counted one
-  if (epi_on && em < M) {
-    if (EPI == DEC_EPI_BIAS) side = to_f32(bias[n]);
-    if (EPI == DEC_EPI_RES) side = to_f32(res[em * ldr + n]);
+  if (tid < 256 * MB && el.m < M) {
+    if (EPI == V3D_DEC_BIAS) side = to_f32(bias[o0 + el.row]);
+    if (EPI == V3D_DEC_RES) side = to_f32(res[el.m * ldr + o0 + el.row]);
   }
   int u = 0;
   for (; u + 1 < nt_w; u += 2) {                            // whole pairs: no branch inside
@@ -640,33 +501,9 @@ __global__ __launch_bounds__(512) void linear_decode_mfma_stream_kernel(const T*
   }
   if (u < nt_w) step(wa, xa, u);
   __syncthreads();                                          // the partial sums reuse the tiles' LDS
-#pragma unroll
-  for (int q = 0; q < SW; ++q)
-#pragma unroll
-    for (int b = 0; b < MB; ++b)
-      *reinterpret_cast<float4*>(part(wave, q, b) + lane * 4) = make_float4(acc[q][b][0], acc[q][b][1], acc[q][b][2], acc[q][b][3]);
-  __syncthreads();
-  if (epi_on) {
-    float v[SW];
-#pragma unroll
-    for (int q = 0; q < SW; ++q) {
-      v[q] = 0.f;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) v[q] += part(w, q, eb)[t8];
-    }
-    if (em < M) {
-      if (EPI == DEC_EPI_SWIGLU) {
-        const float gt = round_to<T>(v[0]), up = round_to<T>(v[SW - 1]);
-        out[em * ldo + n] = from_f32<T>(round_to<T>(silu_f(gt)) * up);
-      } else {
-        float y = v[0];
-        if (EPI == DEC_EPI_BIAS) y += side;
-        y = round_to<T>(y);
-        if (EPI == DEC_EPI_RES) y += side;
-        out[em * ldo + n] = from_f32<T>(y);
-      }
-    }
-  }
+  dec_mfma_tail<T, EPI, MB, 1, false>(tid, lane, wave, acc, part, o0, M, nullptr, [&](float v0, float v1, int m, int n) {
+    out[m * ldo + n] = dec_finish<T, EPI>(v0, v1, side, side);
+  });
 }
 
 // The same weight-streaming linear over OCP e4m3 weights (BASELINE configs[3]): W8 [N, K] bytes with one f32 scale per
@@ -678,19 +515,10 @@ __global__ __launch_bounds__(256, 4) void linear_decode_fp8_kernel(
     const T* __restrict__ x, int64_t ldx, const uint8_t* __restrict__ W, int64_t ldw, const float* __restrict__ sw,
     const T* __restrict__ bias, const T* __restrict__ res, int64_t ldr, T* __restrict__ out, int64_t ldo, int N, int K) {
   __shared__ float red[M][4][4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int kv = K / 16;
   int rows[4];
-  int o0;
-  if (EPI == DEC_EPI_SWIGLU) {
-    o0 = blockIdx.x * 2;
-    rows[0] = (o0 >> 6) * 128 + (o0 & 63); rows[1] = rows[0] + 64;
-    rows[2] = ((o0 + 1) >> 6) * 128 + ((o0 + 1) & 63); rows[3] = rows[2] + 64;
-  } else {
-    o0 = blockIdx.x * 4;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) rows[r] = o0 + r;
-  }
+  const int o0 = dec_valu_rows<EPI>(rows);
   float s[M][4];
 #pragma unroll
   for (int m = 0; m < M; ++m)
@@ -729,41 +557,11 @@ __global__ __launch_bounds__(256, 4) void linear_decode_fp8_kernel(
       }
     }
   }
-#pragma unroll
-  for (int m = 0; m < M; ++m)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) s[m][r] += __shfl_xor(s[m][r], off);
-    }
-  if (lane == 0) {
-#pragma unroll
-    for (int m = 0; m < M; ++m)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) red[m][r][wave] = s[m][r];
-  }
-  __syncthreads();
-  if (EPI == DEC_EPI_SWIGLU) {
-    if (tid < 2 * M) {
-      const int m = tid >> 1, t2 = tid & 1;
-      const float g = round_to<T>((red[m][2 * t2][0] + red[m][2 * t2][1] + red[m][2 * t2][2] + red[m][2 * t2][3]) * sw[rows[2 * t2]]);
-      const float u = round_to<T>((red[m][2 * t2 + 1][0] + red[m][2 * t2 + 1][1] + red[m][2 * t2 + 1][2] + red[m][2 * t2 + 1][3]) * sw[rows[2 * t2 + 1]]);
-      out[m * ldo + o0 + t2] = from_f32<T>(round_to<T>(silu_f(g)) * u);
-    }
-  } else if (tid < 4 * M) {
-    const int m = tid >> 2, r = tid & 3;
-    const int n = o0 + r;
-    float v = (red[m][r][0] + red[m][r][1] + red[m][r][2] + red[m][r][3]) * sw[n];
-    if (EPI == DEC_EPI_BIAS) v += to_f32(bias[n]);
-    v = round_to<T>(v);
-    if (EPI == DEC_EPI_RES) v += to_f32(res[m * ldr + n]);
-    out[m * ldo + n] = from_f32<T>(v);
-  }
+  dec_valu_tail<T, EPI, M, true>(s, red, rows, o0, sw, DecStore<T, EPI>{bias, res, ldr, out, ldo});
 }
 
 // rotary (apply_rotary_pos_emb, modeling_qwen2.py:141-173) on the new token's q and k heads, in place in the
 // QKV row, and append of k (rotated) and v to cache row `pos`:  cache_row = [k heads | v heads].
-constexpr int DEC_MAX_ROWS = 32;     // scenes / questions decoding together (r04: 32; the attention side: DEC_MAXROWS in attention.hip)
 struct RopeRows {        // scenes decoding together (blockIdx.y = scene): own position and cache row
   int pos[DEC_MAX_ROWS];
   void* cache_row[DEC_MAX_ROWS];
@@ -896,9 +694,6 @@ static bool dec_v2_plan(int n_out, int K, int* grid, int* v2_env_out, int* cus_o
 static int linear_decode_rows(const void* x, int64_t ldx, int M, const void* norm_weight, float eps, const void* W, int64_t ldw,
                               const void* bias, const void* res, int64_t ldr, void* out, int64_t ldo, int N, int K, int dtype,
                               int epilogue, void* stream, const char* who) {
-  V3D_REQUIRE(x && W && out, "%s: null pointer", who);
-  V3D_REQUIRE(dtype == V3D_F16 || dtype == V3D_BF16, "%s: dtype must be f16 or bf16", who);
-  V3D_REQUIRE(N > 0 && K > 0 && K % 8 == 0 && ldw % 8 == 0 && ldw >= K, "%s: bad shape N=%d K=%d", who, N, K);
   // one row: the VALU form (fastest for a single scene, fuses the norm); 2..16 rows: the matrix-core form, whose cost does
   // not grow with M and whose columns are independent - a scene's bits are the same in every group of two or more.
   // (Against the one-row form the values differ by the f32 summation order.)  Shapes the matrix-core form does not take
@@ -906,22 +701,17 @@ static int linear_decode_rows(const void* x, int64_t ldx, int M, const void* nor
   // r04: with norm_weight and MORE than four rows the persistent matrix-core form normalises its resident fragments itself (where that
   // form applies: v3d_linear_decode_rows_fuses_norm); up to four rows keep the VALU form, whose rows equal the one-row kernel's bit for bit.
   int v2_grid = 0, v2_env = 1, cus = 256;
-  const bool mfma_shape = K % 128 == 0 && (epilogue == DEC_EPI_SWIGLU ? N % 128 == 0 : N % 16 == 0);
-  const bool v2_ok = mfma_shape && dec_v2_plan(epilogue == DEC_EPI_SWIGLU ? N / 2 : N, K, &v2_grid, &v2_env, &cus);
-  const bool fused_norm = norm_weight && M > 4 && v2_ok && epilogue != DEC_EPI_RES;
+  const int n_out = epilogue == V3D_DEC_SWIGLU ? N / 2 : N;
+  const bool mfma_shape = K % 128 == 0 && (epilogue == V3D_DEC_SWIGLU ? N % 128 == 0 : N % 16 == 0);
+  const bool v2_ok = mfma_shape && dec_v2_plan(n_out, K, &v2_grid, &v2_env, &cus);
+  const bool fused_norm = norm_weight && M > 4 && v2_ok && epilogue != V3D_DEC_RES;
   const bool mfma_ok = mfma_shape && (!norm_weight || fused_norm);
-  const bool mfma = mfma_ok && M >= 2;
-  V3D_REQUIRE(M >= 1 && M <= (mfma_ok ? DEC_MAX_ROWS : 4), "%s: 1 to %d activation rows for this shape (got %d)", who, mfma_ok ? DEC_MAX_ROWS : 4, M);
-  V3D_REQUIRE(N % 4 == 0 && (epilogue != DEC_EPI_SWIGLU || N % 128 == 0), "%s: N=%d not supported", who, N);
-  V3D_REQUIRE(aligned16(x) && aligned16(W) && (!norm_weight || aligned16(norm_weight)), "%s: alignment", who);
-  V3D_REQUIRE(M == 1 || (ldx % 8 == 0 && ldx >= K), "%s: activation row stride %lld", who, (long long)ldx);
-  V3D_REQUIRE(epilogue != DEC_EPI_BIAS || bias, "%s: bias epilogue without bias", who);
-  V3D_REQUIRE(epilogue != DEC_EPI_RES || res, "%s: residual epilogue without residual", who);
+  if (int rc = dec_check_rows(who, x && W && out, dtype, K % 8 == 0 && ldw % 8 == 0 && ldw >= K, mfma_ok,
+                              aligned16(x) && aligned16(W) && (!norm_weight || aligned16(norm_weight)), true, ldx, M, N, K, epilogue, bias, res))
+    return rc;
   V3D_REQUIRE(!norm_weight || K / 8 <= 512, "%s: fused RMSNorm needs K <= 4096 (got %d)", who, K);
   hipStream_t st = (hipStream_t)stream;
-  if (mfma) {
-    V3D_REQUIRE(aligned16(W) && (M == 1 || ldx % 8 == 0), "%s: alignment", who);
-    const int n_out = epilogue == DEC_EPI_SWIGLU ? N / 2 : N;
+  if (mfma_ok && M >= 2) {
     // outputs per workgroup: 16 (r03) or 32.  32 halves the activation bytes every workgroup pulls out of L2 per weight byte, but also the
     // number of workgroups that stream.  Measured (tools/time_decode_rows.py, M = 16 / 32 rows, us; profiles/r04_decode_rows.txt):
     //   LM head  152064 x 3584: 228 -> 188 / 330 -> 260      gate/up 37888 x 3584: 56 -> 60 / 70.5 -> 62      qkv 4608 x 3584: 14.0 -> 11.4 / 20.3 -> 15.4
@@ -930,30 +720,21 @@ static int linear_decode_rows(const void* x, int64_t ldx, int M, const void* nor
     // r04, second session: the pipelined forms (linear_decode_mfma2_kernel / _stream_kernel above; bit-identical outputs).  V3D_DEC_V2 = 0: never;
     // 1 (default): where measured faster (tools/time_decode_rows.py, profiles/r04_decode_rows.txt); 2: wherever the shape allows (tests);
     // 3: the streaming form wherever the shape allows (tests, A/B).
-    const int tiles = K / 128, groups16 = n_out / 16, nt = (tiles + 7) / 8;
+    const int tiles = K / 128, groups16 = n_out / 16, nt = (tiles + 7) / 8, mb = M <= 16 ? 1 : 2;
     if (v2_ok) {
-      const int grid = v2_grid;
-      const bool nrm = fused_norm;
-#define V3D_LD2_L(TT, EE, BB, NN, RR) hipLaunchKernelGGL((linear_decode_mfma2_kernel<TT, EE, BB, NN, RR>), dim3(grid), dim3(512), 0, st, (const TT*)x, ldx, M, \
-                                                     (const TT*)W, ldw, (const TT*)bias, (const TT*)res, ldr, (TT*)out, ldo, K, groups16, (const TT*)norm_weight, eps)
-#define V3D_LD2_K(TT, EE, BB, NN) do { if (nrm && EE != DEC_EPI_RES) V3D_LD2_L(TT, (EE == DEC_EPI_RES ? DEC_EPI_NONE : EE), BB, NN, true); else V3D_LD2_L(TT, EE, BB, NN, false); } while (0)
-#define V3D_LD2_N(TT, EE, BB) { if (nt == 2) V3D_LD2_K(TT, EE, BB, 2); else if (nt == 3) V3D_LD2_K(TT, EE, BB, 3); else V3D_LD2_K(TT, EE, BB, 4); }
-#define V3D_LD2_B(TT, EE) { if (M <= 16) V3D_LD2_N(TT, EE, 1) else V3D_LD2_N(TT, EE, 2) }
-#define V3D_LD2_E(TT)                                                                                 \
-  switch (epilogue) {                                                                                 \
-    case DEC_EPI_NONE: V3D_LD2_B(TT, DEC_EPI_NONE); break; case DEC_EPI_BIAS: V3D_LD2_B(TT, DEC_EPI_BIAS); break; \
-    case DEC_EPI_RES: V3D_LD2_B(TT, DEC_EPI_RES); break; case DEC_EPI_SWIGLU: V3D_LD2_B(TT, DEC_EPI_SWIGLU); break; \
-    default: set_error("%s: unknown epilogue %d", who, epilogue); return V3D_E_INVALID;               \
-  }
-      if (dtype == V3D_BF16) { V3D_LD2_E(bf16_t) } else { V3D_LD2_E(f16_t) }
-#undef V3D_LD2_E
-#undef V3D_LD2_B
-#undef V3D_LD2_N
-#undef V3D_LD2_K
-#undef V3D_LD2_L
-      return check_launch(who);
+      return dec_dispatch(dtype, epilogue, who, [&](auto t, auto e) {
+        using T = decltype(t);
+        constexpr int E = decltype(e)::value;
+        dec_pick<1, 2>(mb, [&](auto b) { dec_pick<2, 3, 4>(nt, [&](auto n) { dec_pick<1, 0>(fused_norm, [&](auto nrm) {
+          constexpr bool NORM = decltype(nrm)::value != 0;
+          if constexpr (!(NORM && E == V3D_DEC_RES))         // fused_norm excludes the residual epilogue: that instantiation is not built
+            hipLaunchKernelGGL((linear_decode_mfma2_kernel<T, E, decltype(b)::value, decltype(n)::value, NORM>), dim3(v2_grid), dim3(512), 0, st,
+                               (const T*)x, ldx, M, (const T*)W, ldw, (const T*)bias, (const T*)res, ldr, (T*)out, ldo, K, groups16,
+                               (const T*)norm_weight, eps);
+        }); }); });
+      });
     }
-    if (v2_env >= 1 && v2_env <= 2 && tiles > 32 && epilogue != DEC_EPI_SWIGLU) {        // K cut into chunks whose activation fragments stay in registers
+    if (v2_env >= 1 && v2_env <= 2 && tiles > 32 && epilogue != V3D_DEC_SWIGLU) {        // K cut into chunks whose activation fragments stay in registers
       int C = 0, hi = 0;
       double best = 0.0;
       for (int c = (tiles + 31) / 32; c <= 16; ++c) {                     // whole rounds of groups on as many CUs as possible
@@ -966,86 +747,56 @@ static int linear_decode_rows(const void* x, int64_t ldx, int M, const void* nor
         if (eff > best + 1e-9) { best = eff; C = c; hi = h; }
       }
       if (C > 0) {
-        const int n_hi = tiles - C * (hi - 1), nt2 = (hi + 7) / 8, mb = M <= 16 ? 1 : 2;
+        const int n_hi = tiles - C * (hi - 1), nt2 = (hi + 7) / 8;
         int G = cus / C;
         if (G > groups16) G = groups16;
         float* ws = decode_split_workspace(st, (size_t)C * 16 * mb * n_out * sizeof(float));
         if (!ws) { set_error("%s: no workspace for the K-split partial sums", who); return V3D_E_LAUNCH; }
-#define V3D_LDK_K(TT, BB, NN) hipLaunchKernelGGL((linear_decode_mfma2_split_kernel<TT, BB, NN>), dim3(G, C), dim3(512), 0, st, (const TT*)x, ldx, M, \
-                                                 (const TT*)W, ldw, ws, groups16, hi, n_hi)
-#define V3D_LDK_N(TT, BB) { if (nt2 == 2) V3D_LDK_K(TT, BB, 2); else if (nt2 == 3) V3D_LDK_K(TT, BB, 3); else V3D_LDK_K(TT, BB, 4); }
-#define V3D_LDK_C(TT, EE) hipLaunchKernelGGL((decode_combine_kernel<TT, EE>), dim3((n_out + 255) / 256, M), dim3(256), 0, st, ws, C, 16 * mb, M, n_out, \
-                                             (const TT*)bias, (const TT*)res, ldr, (TT*)out, ldo)
-#define V3D_LDK_T(TT) { if (mb == 1) V3D_LDK_N(TT, 1) else V3D_LDK_N(TT, 2)                                                         \
-                        if (epilogue == DEC_EPI_BIAS) V3D_LDK_C(TT, DEC_EPI_BIAS); else if (epilogue == DEC_EPI_RES) V3D_LDK_C(TT, DEC_EPI_RES); \
-                        else V3D_LDK_C(TT, DEC_EPI_NONE); }
-        if (dtype == V3D_BF16) V3D_LDK_T(bf16_t) else V3D_LDK_T(f16_t)
-#undef V3D_LDK_T
-#undef V3D_LDK_C
-#undef V3D_LDK_N
-#undef V3D_LDK_K
-        return check_launch(who);
+        return dec_dispatch(dtype, epilogue, who, [&](auto t, auto e) {
+          using T = decltype(t);
+          constexpr int E = decltype(e)::value;
+          if constexpr (E != V3D_DEC_SWIGLU) {                            // (SwiGLU never comes here: no combine kernel is built for it)
+            dec_pick<1, 2>(mb, [&](auto b) { dec_pick<2, 3, 4>(nt2, [&](auto n) {
+              hipLaunchKernelGGL((linear_decode_mfma2_split_kernel<T, decltype(b)::value, decltype(n)::value>), dim3(G, C), dim3(512), 0, st,
+                                 (const T*)x, ldx, M, (const T*)W, ldw, ws, groups16, hi, n_hi);
+            }); });
+            hipLaunchKernelGGL((decode_combine_kernel<T, E>), dim3((n_out + 255) / 256, M), dim3(256), 0, st, ws, C, 16 * mb, M, n_out,
+                               (const T*)bias, (const T*)res, ldr, (T*)out, ldo);
+          }
+        });
       }
     }
     if (v2_env >= 2 && tiles >= 8) {     // the streaming form ties the r04 kernel on down_proj (47 vs 45.5 us at 32 rows): tests and A/B only
                                          // (every wave needs a tile: the unconditional requests clamp to its last one)
-#define V3D_LDS_B(TT, EE) { if (M <= 16) hipLaunchKernelGGL((linear_decode_mfma_stream_kernel<TT, EE, 1>), dim3(groups16), dim3(512), 0, st, (const TT*)x, ldx, M, \
-                                                     (const TT*)W, ldw, (const TT*)bias, (const TT*)res, ldr, (TT*)out, ldo, K);                            \
-                            else hipLaunchKernelGGL((linear_decode_mfma_stream_kernel<TT, EE, 2>), dim3(groups16), dim3(512), 0, st, (const TT*)x, ldx, M,     \
-                                                     (const TT*)W, ldw, (const TT*)bias, (const TT*)res, ldr, (TT*)out, ldo, K); }
-#define V3D_LDS_E(TT)                                                                                 \
-  switch (epilogue) {                                                                                 \
-    case DEC_EPI_NONE: V3D_LDS_B(TT, DEC_EPI_NONE); break; case DEC_EPI_BIAS: V3D_LDS_B(TT, DEC_EPI_BIAS); break; \
-    case DEC_EPI_RES: V3D_LDS_B(TT, DEC_EPI_RES); break; case DEC_EPI_SWIGLU: V3D_LDS_B(TT, DEC_EPI_SWIGLU); break; \
-    default: set_error("%s: unknown epilogue %d", who, epilogue); return V3D_E_INVALID;               \
-  }
-      if (dtype == V3D_BF16) { V3D_LDS_E(bf16_t) } else { V3D_LDS_E(f16_t) }
-#undef V3D_LDS_E
-#undef V3D_LDS_B
-      return check_launch(who);
+      return dec_dispatch(dtype, epilogue, who, [&](auto t, auto e) {
+        using T = decltype(t);
+        dec_pick<1, 2>(mb, [&](auto b) {
+          hipLaunchKernelGGL((linear_decode_mfma_stream_kernel<T, decltype(e)::value, decltype(b)::value>), dim3(groups16), dim3(512), 0, st,
+                             (const T*)x, ldx, M, (const T*)W, ldw, (const T*)bias, (const T*)res, ldr, (T*)out, ldo, K);
+        });
+      });
     }
     static int og_env = -1;
     if (og_env < 0) { const char* e = getenv("V3D_DEC_OG"); og_env = e ? atoi(e) : 2; }
     const int wg32 = n_out / 32;
     const bool og_rule = wg32 >= 128 && !(wg32 >= 256 && wg32 < 1024 && M <= 16);
     const int og = (og_env >= 2 && n_out % 32 == 0 && (og_env >= 3 || og_rule)) ? 2 : 1;
-    const int mblocks = n_out / (16 * og);
-#define V3D_LDM_B(TT, EE, BB, GG) hipLaunchKernelGGL((linear_decode_mfma_kernel<TT, EE, BB, GG>), dim3(mblocks), dim3(512), 0, st, (const TT*)x, ldx, M, \
-                                                     (const TT*)W, ldw, (const TT*)bias, (const TT*)res, ldr, (TT*)out, ldo, N, K)
-#define V3D_LDM(TT, EE) { if (M <= 16) { if (og == 2) V3D_LDM_B(TT, EE, 1, 2); else V3D_LDM_B(TT, EE, 1, 1); }                       \
-                          else { if (og == 2) V3D_LDM_B(TT, EE, 2, 2); else V3D_LDM_B(TT, EE, 2, 1); } }
-#define V3D_LDM_E(TT)                                                                                 \
-  switch (epilogue) {                                                                                 \
-    case DEC_EPI_NONE: V3D_LDM(TT, DEC_EPI_NONE); break; case DEC_EPI_BIAS: V3D_LDM(TT, DEC_EPI_BIAS); break; \
-    case DEC_EPI_RES: V3D_LDM(TT, DEC_EPI_RES); break; case DEC_EPI_SWIGLU: V3D_LDM(TT, DEC_EPI_SWIGLU); break; \
-    default: set_error("%s: unknown epilogue %d", who, epilogue); return V3D_E_INVALID;               \
+    return dec_dispatch(dtype, epilogue, who, [&](auto t, auto e) {
+      using T = decltype(t);
+      dec_pick<1, 2>(mb, [&](auto b) { dec_pick<2, 1>(og, [&](auto g) {
+        hipLaunchKernelGGL((linear_decode_mfma_kernel<T, decltype(e)::value, decltype(b)::value, decltype(g)::value>), dim3(n_out / (16 * og)),
+                           dim3(512), 0, st, (const T*)x, ldx, M, (const T*)W, ldw, (const T*)bias, (const T*)res, ldr, (T*)out, ldo, N, K);
+      }); });
+    });
   }
-    if (dtype == V3D_BF16) { V3D_LDM_E(bf16_t) } else { V3D_LDM_E(f16_t) }
-#undef V3D_LDM_E
-#undef V3D_LDM
-#undef V3D_LDM_B
-    return check_launch(who);
-  }
-  const int blocks = N / 4;                                   // 4 weight rows per workgroup (SWIGLU: 2 gate/up pairs)
-#define V3D_LD(TT, EE, NN, MM)                                                                                                \
-  hipLaunchKernelGGL((linear_decode_kernel<TT, EE, NN, MM>), dim3(blocks), dim3(256), 0, st, (const TT*)x, ldx, (const TT*)norm_weight, \
-                     eps, (const TT*)W, ldw, (const TT*)bias, (const TT*)res, ldr, (TT*)out, ldo, N, K)
-#define V3D_LD_M(TT, EE, NN)                                                                          \
-  switch (M) { case 1: V3D_LD(TT, EE, NN, 1); break; case 2: V3D_LD(TT, EE, NN, 2); break;            \
-               case 3: V3D_LD(TT, EE, NN, 3); break; default: V3D_LD(TT, EE, NN, 4); break; }
-#define V3D_LD_N(TT, EE) { if (norm_weight) { V3D_LD_M(TT, EE, true) } else { V3D_LD_M(TT, EE, false) } }
-#define V3D_LD_E(TT)                                                                                  \
-  switch (epilogue) {                                                                                 \
-    case DEC_EPI_NONE: V3D_LD_N(TT, DEC_EPI_NONE) break; case DEC_EPI_BIAS: V3D_LD_N(TT, DEC_EPI_BIAS) break; \
-    case DEC_EPI_RES: V3D_LD_N(TT, DEC_EPI_RES) break; case DEC_EPI_SWIGLU: V3D_LD_N(TT, DEC_EPI_SWIGLU) break; \
-    default: set_error("%s: unknown epilogue %d", who, epilogue); return V3D_E_INVALID;               \
-  }
-  if (dtype == V3D_BF16) { V3D_LD_E(bf16_t) } else { V3D_LD_E(f16_t) }
-#undef V3D_LD_E
-#undef V3D_LD_N
-#undef V3D_LD_M
-#undef V3D_LD
-  return check_launch(who);
+  return dec_dispatch(dtype, epilogue, who, [&](auto t, auto e) {
+    using T = decltype(t);
+    dec_pick<1, 0>(norm_weight != nullptr, [&](auto nrm) { dec_pick<1, 2, 3, 4>(M, [&](auto m) {
+      hipLaunchKernelGGL((linear_decode_kernel<T, decltype(e)::value, decltype(nrm)::value != 0, decltype(m)::value>), dim3(N / 4), dim3(256), 0,
+                         st, (const T*)x, ldx, (const T*)norm_weight, eps, (const T*)W, ldw, (const T*)bias, (const T*)res, ldr, (T*)out, ldo,
+                         N, K);                               // 4 weight rows per workgroup (SWIGLU: 2 gate/up pairs)
+    }); });
+  });
 }
 
 extern "C" int v3d_linear_decode(const void* x, const void* norm_weight, float eps, const void* W, int64_t ldw,
@@ -1057,9 +808,9 @@ extern "C" int v3d_linear_decode(const void* x, const void* norm_weight, float e
 extern "C" int v3d_linear_decode_rows_fuses_norm(int M, int N, int K, int epilogue) {
   const char* off = getenv("V3D_DEC_FUSE_NORM");           // "0": callers normalise first (A/B)
   if (off && atoi(off) == 0) return 0;
-  const bool mfma_shape = K % 128 == 0 && (epilogue == DEC_EPI_SWIGLU ? N % 128 == 0 : N % 16 == 0);
-  return (M > 4 && M <= DEC_MAX_ROWS && K <= 4096 && epilogue != DEC_EPI_RES && mfma_shape &&
-          dec_v2_plan(epilogue == DEC_EPI_SWIGLU ? N / 2 : N, K, nullptr, nullptr, nullptr)) ? 1 : 0;
+  const bool mfma_shape = K % 128 == 0 && (epilogue == V3D_DEC_SWIGLU ? N % 128 == 0 : N % 16 == 0);
+  return (M > 4 && M <= DEC_MAX_ROWS && K <= 4096 && epilogue != V3D_DEC_RES && mfma_shape &&
+          dec_v2_plan(epilogue == V3D_DEC_SWIGLU ? N / 2 : N, K, nullptr, nullptr, nullptr)) ? 1 : 0;
 }
 
 extern "C" int v3d_linear_decode_rows(const void* x, int64_t ldx, int M, const void* norm_weight, float eps, const void* W,
@@ -1091,7 +842,7 @@ __global__ __launch_bounds__(512) void linear_decode_fp8_mfma_kernel(const T* __
                                                                      int64_t ldw, const float* __restrict__ sw, const T* __restrict__ bias,
                                                                      const T* __restrict__ res, int64_t ldr, T* __restrict__ out, int64_t ldo,
                                                                      int N, int K) {
-  constexpr int RG = EPI == DEC_EPI_SWIGLU ? 2 : 1;
+  constexpr int RG = EPI == V3D_DEC_SWIGLU ? 2 : 1;
   constexpr int PITCH = 272;
   __shared__ __attribute__((aligned(16))) char tile[8][RG][16 * PITCH];
   __shared__ float part[8][RG][MB][256];
@@ -1099,19 +850,12 @@ __global__ __launch_bounds__(512) void linear_decode_fp8_mfma_kernel(const T* __
   const int r = lane & 15, g = lane >> 4;
   const int lr = lane >> 4, lc = lane & 15;
   const int o0 = blockIdx.x * 16;
-  int row0[RG];
-  if (EPI == DEC_EPI_SWIGLU) { row0[0] = (o0 >> 6) * 128 + (o0 & 63); row0[RG - 1] = row0[0] + 64; }
-  else row0[0] = o0;
   const uint8_t* wbase[RG];
 #pragma unroll
-  for (int q = 0; q < RG; ++q) wbase[q] = W + (int64_t)(row0[q] + lr) * ldw + 16 * lc;
+  for (int q = 0; q < RG; ++q) wbase[q] = W + (int64_t)(dec_row0<EPI>(o0) + 64 * q + lr) * ldw + 16 * lc;
   bool col_ok[MB];
   const T* xrow[MB];
-#pragma unroll
-  for (int b = 0; b < MB; ++b) {
-    col_ok[b] = r + 16 * b < M;
-    xrow[b] = x + (int64_t)(col_ok[b] ? r + 16 * b : 0) * ldx + 8 * g;
-  }
+  dec_x_rows(x, ldx, M, r, 8 * g, col_ok, xrow);
   dec_f32x4 acc[RG][MB];
 #pragma unroll
   for (int q = 0; q < RG; ++q)
@@ -1147,92 +891,36 @@ __global__ __launch_bounds__(512) void linear_decode_fp8_mfma_kernel(const T* __
         for (int b = 0; b < MB; ++b) acc[q][b] = dec_mfma(T{}, a, xb[b][t], acc[q][b]);
       }
   }
-#pragma unroll
-  for (int q = 0; q < RG; ++q)
-#pragma unroll
-    for (int b = 0; b < MB; ++b)
-      *reinterpret_cast<float4*>(&part[wave][q][b][lane * 4]) = make_float4(acc[q][b][0], acc[q][b][1], acc[q][b][2], acc[q][b][3]);
-  __syncthreads();
-  for (int e = tid; e < 256 * MB; e += 512) {
-    const int b = e >> 8, t8 = e & 255;
-    const int l = t8 >> 2, i = t8 & 3;
-    const int row = 4 * (l >> 4) + i, m = (l & 15) + 16 * b;
-    float v[RG];
-#pragma unroll
-    for (int q = 0; q < RG; ++q) {
-      v[q] = 0.f;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) v[q] += part[w][q][b][t8];
-      v[q] *= sw[row0[q] + row];
-    }
-    if (m < M) {
-      const int n = o0 + row;
-      if (EPI == DEC_EPI_SWIGLU) {
-        const float gt = round_to<T>(v[0]), up = round_to<T>(v[RG - 1]);
-        out[m * ldo + n] = from_f32<T>(round_to<T>(silu_f(gt)) * up);
-      } else {
-        float y = v[0];
-        if (EPI == DEC_EPI_BIAS) y += to_f32(bias[n]);
-        y = round_to<T>(y);
-        if (EPI == DEC_EPI_RES) y += to_f32(res[m * ldr + n]);
-        out[m * ldo + n] = from_f32<T>(y);
-      }
-    }
-  }
+  dec_mfma_tail<T, EPI, MB, 1, true>(tid, lane, wave, acc, [&](int w, int q, int b) { return &part[w][q][b][0]; }, o0, M, sw,
+                                     DecStore<T, EPI>{bias, res, ldr, out, ldo});
 }
 
 extern "C" int v3d_linear_decode_fp8_rows(const void* x, int64_t ldx, int M, const void* W8, int64_t ldw, const float* scale_w,
                                           const void* bias, const void* res, int64_t ldr, void* out, int64_t ldo, int N, int K,
                                           int dtype, int epilogue, void* stream) {
   const char* who = "v3d_linear_decode_fp8_rows";
-  V3D_REQUIRE(x && W8 && scale_w && out, "%s: null pointer", who);
-  V3D_REQUIRE(dtype == V3D_F16 || dtype == V3D_BF16, "%s: dtype must be f16 or bf16", who);
-  V3D_REQUIRE(N > 0 && K > 0 && K % 16 == 0 && ldw % 16 == 0 && ldw >= K, "%s: bad shape N=%d K=%d", who, N, K);
   // one row: VALU form; 2..16 rows: matrix-core form when the shape allows (a row's bits then depend neither on the other
   // rows nor on M); other shapes: VALU form with up to 4 rows
-  const bool mfma_ok = K % 256 == 0 && (epilogue == DEC_EPI_SWIGLU ? N % 128 == 0 : N % 16 == 0);
-  const bool mfma = mfma_ok && M >= 2;
-  V3D_REQUIRE(M >= 1 && M <= (mfma_ok ? DEC_MAX_ROWS : 4), "%s: 1 to %d activation rows for this shape (got %d)", who, mfma_ok ? DEC_MAX_ROWS : 4, M);
-  V3D_REQUIRE(N % 4 == 0 && (epilogue != DEC_EPI_SWIGLU || N % 128 == 0), "%s: N=%d not supported", who, N);
-  V3D_REQUIRE(aligned16(x) && aligned16(W8) && (M == 1 || (ldx % 8 == 0 && ldx >= K)), "%s: alignment", who);
-  V3D_REQUIRE(epilogue != DEC_EPI_BIAS || bias, "%s: bias epilogue without bias", who);
-  V3D_REQUIRE(epilogue != DEC_EPI_RES || res, "%s: residual epilogue without residual", who);
+  const bool mfma_ok = K % 256 == 0 && (epilogue == V3D_DEC_SWIGLU ? N % 128 == 0 : N % 16 == 0);
+  if (int rc = dec_check_rows(who, x && W8 && scale_w && out, dtype, K % 16 == 0 && ldw % 16 == 0 && ldw >= K, mfma_ok, aligned16(x) && aligned16(W8),
+                              false, ldx, M, N, K, epilogue, bias, res))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (mfma) {
-    const int mblocks = (epilogue == DEC_EPI_SWIGLU ? N / 2 : N) / 16;
-#define V3D_LD8M_B(TT, EE, BB) hipLaunchKernelGGL((linear_decode_fp8_mfma_kernel<TT, EE, BB>), dim3(mblocks), dim3(512), 0, st, (const TT*)x, ldx, M, \
-                                                  (const uint8_t*)W8, ldw, scale_w, (const TT*)bias, (const TT*)res, ldr, (TT*)out, ldo, N, K)
-#define V3D_LD8M(TT, EE) { if (M <= 16) V3D_LD8M_B(TT, EE, 1); else V3D_LD8M_B(TT, EE, 2); }
-#define V3D_LD8M_E(TT)                                                                                \
-  switch (epilogue) {                                                                                 \
-    case DEC_EPI_NONE: V3D_LD8M(TT, DEC_EPI_NONE); break; case DEC_EPI_BIAS: V3D_LD8M(TT, DEC_EPI_BIAS); break; \
-    case DEC_EPI_RES: V3D_LD8M(TT, DEC_EPI_RES); break; case DEC_EPI_SWIGLU: V3D_LD8M(TT, DEC_EPI_SWIGLU); break; \
-    default: set_error("%s: unknown epilogue %d", who, epilogue); return V3D_E_INVALID;               \
-  }
-    if (dtype == V3D_BF16) { V3D_LD8M_E(bf16_t) } else { V3D_LD8M_E(f16_t) }
-#undef V3D_LD8M_E
-#undef V3D_LD8M
-#undef V3D_LD8M_B
-    return check_launch(who);
-  }
-  const int blocks = N / 4;
-#define V3D_LD8(TT, EE, MM)                                                                                                   \
-  hipLaunchKernelGGL((linear_decode_fp8_kernel<TT, EE, MM>), dim3(blocks), dim3(256), 0, st, (const TT*)x, ldx, (const uint8_t*)W8, ldw, \
-                     scale_w, (const TT*)bias, (const TT*)res, ldr, (TT*)out, ldo, N, K)
-#define V3D_LD8_M(TT, EE)                                                                             \
-  switch (M) { case 1: V3D_LD8(TT, EE, 1); break; case 2: V3D_LD8(TT, EE, 2); break;                  \
-               case 3: V3D_LD8(TT, EE, 3); break; default: V3D_LD8(TT, EE, 4); break; }
-#define V3D_LD8_E(TT)                                                                                 \
-  switch (epilogue) {                                                                                 \
-    case DEC_EPI_NONE: V3D_LD8_M(TT, DEC_EPI_NONE) break; case DEC_EPI_BIAS: V3D_LD8_M(TT, DEC_EPI_BIAS) break; \
-    case DEC_EPI_RES: V3D_LD8_M(TT, DEC_EPI_RES) break; case DEC_EPI_SWIGLU: V3D_LD8_M(TT, DEC_EPI_SWIGLU) break; \
-    default: set_error("%s: unknown epilogue %d", who, epilogue); return V3D_E_INVALID;               \
-  }
-  if (dtype == V3D_BF16) { V3D_LD8_E(bf16_t) } else { V3D_LD8_E(f16_t) }
-#undef V3D_LD8_E
-#undef V3D_LD8_M
-#undef V3D_LD8
-  return check_launch(who);
+  return dec_dispatch(dtype, epilogue, who, [&](auto t, auto e) {
+    using T = decltype(t);
+    constexpr int E = decltype(e)::value;
+    if (mfma_ok && M >= 2) {
+      dec_pick<1, 2>(M <= 16 ? 1 : 2, [&](auto b) {
+        hipLaunchKernelGGL((linear_decode_fp8_mfma_kernel<T, E, decltype(b)::value>), dim3((E == V3D_DEC_SWIGLU ? N / 2 : N) / 16), dim3(512), 0, st,
+                           (const T*)x, ldx, M, (const uint8_t*)W8, ldw, scale_w, (const T*)bias, (const T*)res, ldr, (T*)out, ldo, N, K);
+      });
+    } else {
+      dec_pick<1, 2, 3, 4>(M, [&](auto m) {
+        hipLaunchKernelGGL((linear_decode_fp8_kernel<T, E, decltype(m)::value>), dim3(N / 4), dim3(256), 0, st, (const T*)x, ldx, (const uint8_t*)W8,
+                           ldw, scale_w, (const T*)bias, (const T*)res, ldr, (T*)out, ldo, N, K);
+      });
+    }
+  });
 }
 
 static int rope_kv_append_rows(void* qkv, int64_t qkv_stride, int M, int n_q_heads, int n_kv_heads, int head_dim, const void* cos_table,

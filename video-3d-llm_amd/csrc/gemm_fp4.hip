@@ -30,15 +30,11 @@
 // LDS with the weight DMA, or repack the exponents at load so that a lane's four bytes are one dword; the freed LDS also allows
 // a third stage.
 #include "gemm_q8_tile.h"
+#include "decode_common.h"
 
 namespace v3d {
 
-using f4_f32x4 = __attribute__((ext_vector_type(4))) float;
 using f4_f32x2 = __attribute__((ext_vector_type(2))) float;
-
-enum { F4_DEC_NONE = 0, F4_DEC_BIAS = 1, F4_DEC_RES = 2, F4_DEC_SWIGLU = 3 };
-
-__device__ __forceinline__ float silu4_dec(float x) { return x / (1.0f + __expf(-x)); }
 
 template <typename T, int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_mxfp4_kernel(Q8GemmArgs p) { q8_gemm_tile<T, EPI, WfMxfp4>(p); }
@@ -80,15 +76,7 @@ __global__ __launch_bounds__(256) void quantize_mxfp4_kernel(const T* __restrict
   if ((c & 3) == 0) e[row * lde + (c >> 2)] = (uint8_t)ex;
 }
 
-// ---- decode linears (W4A16) ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint4 ldg_nt4(const uint4* p) {
-  uint4 r;
-  r.x = __builtin_nontemporal_load(&p->x);
-  r.y = __builtin_nontemporal_load(&p->y);
-  r.z = __builtin_nontemporal_load(&p->z);
-  r.w = __builtin_nontemporal_load(&p->w);
-  return r;
-}
+// ---- decode linears (W4A16; the parts around the K loops are decode_common.h's) -------------------------------------------------
 __device__ __forceinline__ float f4_scale(uint32_t e) { return __uint_as_float(e << 23); }     // only the exponent field is read
 
 // 8 codes (one 32-bit word, k ascending from the low nibble) times 2^(e-127), as 8 values of the activation type
@@ -105,15 +93,6 @@ __device__ __forceinline__ uint4 f4_widen8(f16_t, uint32_t w, float sc) {
   return make_uint4(__builtin_bit_cast(uint32_t, p0), __builtin_bit_cast(uint32_t, p1), __builtin_bit_cast(uint32_t, p2), __builtin_bit_cast(uint32_t, p3));
 }
 
-using f4_bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using f4_f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-__device__ __forceinline__ f4_f32x4 f4_mfma16(bf16_t, const uint4& a, const uint4& b, f4_f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(f4_bf16x8, a), __builtin_bit_cast(f4_bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f4_f32x4 f4_mfma16(f16_t, const uint4& a, const uint4& b, f4_f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f4_f16x8, a), __builtin_bit_cast(f4_f16x8, b), c, 0, 0, 0);
-}
-
 // VALU form (one row; up to 4 rows for shapes without a matrix-core form): linear_decode_fp8_kernel over 4-bit codes.  Workgroup =
 // 4 waves = FOUR weight rows, K split over the 256 threads in 16-byte chunks = 32 weights = exactly one MX block; the codes are
 // widened to f32 with their block scale by v_cvt_scalef32_pk_f32_fp4 (exact).  Each activation row's arithmetic is the M = 1
@@ -123,19 +102,10 @@ __global__ __launch_bounds__(256, 4) void linear_decode_mxfp4_kernel(
     const T* __restrict__ x, int64_t ldx, const uint8_t* __restrict__ W, int64_t ldw, const uint8_t* __restrict__ E, int64_t lde,
     const T* __restrict__ bias, const T* __restrict__ res, int64_t ldr, T* __restrict__ out, int64_t ldo, int N, int K) {
   __shared__ float red[M][4][4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int kv = K / 32;
   int rows[4];
-  int o0;
-  if (EPI == F4_DEC_SWIGLU) {
-    o0 = blockIdx.x * 2;
-    rows[0] = (o0 >> 6) * 128 + (o0 & 63); rows[1] = rows[0] + 64;
-    rows[2] = ((o0 + 1) >> 6) * 128 + ((o0 + 1) & 63); rows[3] = rows[2] + 64;
-  } else {
-    o0 = blockIdx.x * 4;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) rows[r] = o0 + r;
-  }
+  const int o0 = dec_valu_rows<EPI>(rows);
   float s[M][4];
 #pragma unroll
   for (int m = 0; m < M; ++m)
@@ -149,7 +119,7 @@ __global__ __launch_bounds__(256, 4) void linear_decode_mxfp4_kernel(
     uint4 w4[4];
     float sc[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { w4[r] = ldg_nt4(wr[r] + k); sc[r] = f4_scale(__builtin_nontemporal_load(er[r] + k)); }
+    for (int r = 0; r < 4; ++r) { w4[r] = ldg_nt(wr[r] + k); sc[r] = f4_scale(__builtin_nontemporal_load(er[r] + k)); }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {                   // 8 weights of each row against 8 activations of each activation row
       uint4 xv[M];
@@ -174,36 +144,7 @@ __global__ __launch_bounds__(256, 4) void linear_decode_mxfp4_kernel(
       }
     }
   }
-#pragma unroll
-  for (int m = 0; m < M; ++m)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) s[m][r] += __shfl_xor(s[m][r], off);
-    }
-  if (lane == 0) {
-#pragma unroll
-    for (int m = 0; m < M; ++m)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) red[m][r][wave] = s[m][r];
-  }
-  __syncthreads();
-  if (EPI == F4_DEC_SWIGLU) {
-    if (tid < 2 * M) {
-      const int m = tid >> 1, t2 = tid & 1;
-      const float g = round_to<T>(red[m][2 * t2][0] + red[m][2 * t2][1] + red[m][2 * t2][2] + red[m][2 * t2][3]);
-      const float u = round_to<T>(red[m][2 * t2 + 1][0] + red[m][2 * t2 + 1][1] + red[m][2 * t2 + 1][2] + red[m][2 * t2 + 1][3]);
-      out[m * ldo + o0 + t2] = from_f32<T>(round_to<T>(silu4_dec(g)) * u);
-    }
-  } else if (tid < 4 * M) {
-    const int m = tid >> 2, r = tid & 3;
-    const int n = o0 + r;
-    float v = red[m][r][0] + red[m][r][1] + red[m][r][2] + red[m][r][3];
-    if (EPI == F4_DEC_BIAS) v += to_f32(bias[n]);
-    v = round_to<T>(v);
-    if (EPI == F4_DEC_RES) v += to_f32(res[m * ldr + n]);
-    out[m * ldo + n] = from_f32<T>(v);
-  }
+  dec_valu_tail<T, EPI, M, false>(s, red, rows, o0, nullptr, DecStore<T, EPI>{bias, res, ldr, out, ldo});
 }
 
 // Matrix-core form (2..32 rows), as linear_decode_fp8_mfma_kernel: a workgroup owns 16 outputs (SwiGLU: 16 gate + 16 up rows), its 8
@@ -216,7 +157,7 @@ __global__ __launch_bounds__(512) void linear_decode_mxfp4_mfma_kernel(const T* 
                                                                        int64_t ldw, const uint8_t* __restrict__ E, int64_t lde,
                                                                        const T* __restrict__ bias, const T* __restrict__ res, int64_t ldr,
                                                                        T* __restrict__ out, int64_t ldo, int N, int K) {
-  constexpr int RG = EPI == F4_DEC_SWIGLU ? 2 : 1;
+  constexpr int RG = EPI == V3D_DEC_SWIGLU ? 2 : 1;
   constexpr int PITCH = 144;
   __shared__ __attribute__((aligned(16))) char tile[8][RG][16 * PITCH];
   __shared__ float part[8][RG][MB][256];
@@ -224,28 +165,21 @@ __global__ __launch_bounds__(512) void linear_decode_mxfp4_mfma_kernel(const T* 
   const int r = lane & 15, g = lane >> 4;
   const int lr = lane >> 3, lc = lane & 7;
   const int o0 = blockIdx.x * 16;
-  int row0[RG];
-  if (EPI == F4_DEC_SWIGLU) { row0[0] = (o0 >> 6) * 128 + (o0 & 63); row0[RG - 1] = row0[0] + 64; }
-  else row0[0] = o0;
   const uint8_t* wbase[RG];
   const uint8_t* ebase[RG];
 #pragma unroll
   for (int q = 0; q < RG; ++q) {
-    wbase[q] = W + (int64_t)(row0[q] + lr) * ldw + 16 * lc;
-    ebase[q] = E + (int64_t)(row0[q] + r) * lde;
+    wbase[q] = W + (int64_t)(dec_row0<EPI>(o0) + 64 * q + lr) * ldw + 16 * lc;
+    ebase[q] = E + (int64_t)(dec_row0<EPI>(o0) + 64 * q + r) * lde;
   }
   bool col_ok[MB];
   const T* xrow[MB];
-#pragma unroll
-  for (int b = 0; b < MB; ++b) {
-    col_ok[b] = r + 16 * b < M;
-    xrow[b] = x + (int64_t)(col_ok[b] ? r + 16 * b : 0) * ldx + 8 * g;
-  }
-  f4_f32x4 acc[RG][MB];
+  dec_x_rows(x, ldx, M, r, 8 * g, col_ok, xrow);
+  dec_f32x4 acc[RG][MB];
 #pragma unroll
   for (int q = 0; q < RG; ++q)
 #pragma unroll
-    for (int b = 0; b < MB; ++b) acc[q][b] = f4_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int b = 0; b < MB; ++b) acc[q][b] = dec_f32x4{0.f, 0.f, 0.f, 0.f};
   const int tiles = K / 256;
   for (int s = wave; s < tiles; s += 8) {
     const int k0 = 256 * s;
@@ -254,7 +188,7 @@ __global__ __launch_bounds__(512) void linear_decode_mxfp4_mfma_kernel(const T* 
 #pragma unroll
     for (int q = 0; q < RG; ++q) {
 #pragma unroll
-      for (int j = 0; j < 2; ++j) wreg[q][j] = ldg_nt4(reinterpret_cast<const uint4*>(wbase[q] + (int64_t)(8 * j) * ldw + k0 / 2));
+      for (int j = 0; j < 2; ++j) wreg[q][j] = ldg_nt(reinterpret_cast<const uint4*>(wbase[q] + (int64_t)(8 * j) * ldw + k0 / 2));
       const uint32_t* ep = reinterpret_cast<const uint32_t*>(ebase[q] + k0 / 32);
       ex[q][0] = __builtin_nontemporal_load(ep); ex[q][1] = __builtin_nontemporal_load(ep + 1);
     }
@@ -277,40 +211,11 @@ __global__ __launch_bounds__(512) void linear_decode_mxfp4_mfma_kernel(const T* 
         const uint32_t w4 = *reinterpret_cast<const uint32_t*>(&tile[wave][q][r * PITCH + (4 * t + g) * 4]);
         const uint4 a = f4_widen8(T{}, w4, f4_scale((ex[q][t >> 2] >> (8 * (t & 3))) & 0xffu));
 #pragma unroll
-        for (int b = 0; b < MB; ++b) acc[q][b] = f4_mfma16(T{}, a, xb[b][t], acc[q][b]);
+        for (int b = 0; b < MB; ++b) acc[q][b] = dec_mfma(T{}, a, xb[b][t], acc[q][b]);
       }
   }
-#pragma unroll
-  for (int q = 0; q < RG; ++q)
-#pragma unroll
-    for (int b = 0; b < MB; ++b)
-      *reinterpret_cast<float4*>(&part[wave][q][b][lane * 4]) = make_float4(acc[q][b][0], acc[q][b][1], acc[q][b][2], acc[q][b][3]);
-  __syncthreads();
-  for (int e = tid; e < 256 * MB; e += 512) {
-    const int b = e >> 8, t8 = e & 255;
-    const int l = t8 >> 2, i = t8 & 3;
-    const int row = 4 * (l >> 4) + i, m = (l & 15) + 16 * b;
-    float v[RG];
-#pragma unroll
-    for (int q = 0; q < RG; ++q) {
-      v[q] = 0.f;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) v[q] += part[w][q][b][t8];
-    }
-    if (m < M) {
-      const int n = o0 + row;
-      if (EPI == F4_DEC_SWIGLU) {
-        const float gt = round_to<T>(v[0]), up = round_to<T>(v[RG - 1]);
-        out[m * ldo + n] = from_f32<T>(round_to<T>(silu4_dec(gt)) * up);
-      } else {
-        float y = v[0];
-        if (EPI == F4_DEC_BIAS) y += to_f32(bias[n]);
-        y = round_to<T>(y);
-        if (EPI == F4_DEC_RES) y += to_f32(res[m * ldr + n]);
-        out[m * ldo + n] = from_f32<T>(y);
-      }
-    }
-  }
+  dec_mfma_tail<T, EPI, MB, 1, false>(tid, lane, wave, acc, [&](int w, int q, int b) { return &part[w][q][b][0]; }, o0, M, nullptr,
+                                      DecStore<T, EPI>{bias, res, ldr, out, ldo});
 }
 
 template <typename T>
@@ -352,53 +257,28 @@ extern "C" int v3d_linear_decode_mxfp4_rows(const void* x, int64_t ldx, int M, c
                                             const void* bias, const void* res, int64_t ldr, void* out, int64_t ldo, int N, int K, int dtype,
                                             int epilogue, void* stream) {
   const char* who = "v3d_linear_decode_mxfp4_rows";
-  V3D_REQUIRE(x && Wq && We && out, "%s: null pointer", who);
-  V3D_REQUIRE(dtype == V3D_F16 || dtype == V3D_BF16, "%s: dtype must be f16 or bf16", who);
-  V3D_REQUIRE(N > 0 && K > 0 && K % 128 == 0 && ldw % 16 == 0 && ldw >= K / 2 && lde >= K / 32, "%s: bad shape N=%d K=%d", who, N, K);
   // one row: VALU form; 2..32 rows: matrix-core form when the shape allows (a row's bits then depend neither on the other rows
   // nor on M); other shapes: VALU form with up to 4 rows
   const bool mfma_ok = K % 256 == 0 && lde % 8 == 0 && (reinterpret_cast<uintptr_t>(We) & 7) == 0 &&
-                       (epilogue == F4_DEC_SWIGLU ? N % 128 == 0 : N % 16 == 0);
-  const bool mfma = mfma_ok && M >= 2;
-  V3D_REQUIRE(M >= 1 && M <= (mfma_ok ? 32 : 4), "%s: 1 to %d activation rows for this shape (got %d)", who, mfma_ok ? 32 : 4, M);
-  V3D_REQUIRE(N % 4 == 0 && (epilogue != F4_DEC_SWIGLU || N % 128 == 0), "%s: N=%d not supported", who, N);
-  V3D_REQUIRE(aligned16(x) && aligned16(Wq) && (M == 1 || (ldx % 8 == 0 && ldx >= K)), "%s: alignment", who);
-  V3D_REQUIRE(epilogue != F4_DEC_BIAS || bias, "%s: bias epilogue without bias", who);
-  V3D_REQUIRE(epilogue != F4_DEC_RES || res, "%s: residual epilogue without residual", who);
+                       (epilogue == V3D_DEC_SWIGLU ? N % 128 == 0 : N % 16 == 0);
+  if (int rc = dec_check_rows(who, x && Wq && We && out, dtype, K % 128 == 0 && ldw % 16 == 0 && ldw >= K / 2 && lde >= K / 32, mfma_ok,
+                              aligned16(x) && aligned16(Wq), false, ldx, M, N, K, epilogue, bias, res))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (mfma) {
-    const int mblocks = (epilogue == F4_DEC_SWIGLU ? N / 2 : N) / 16;
-#define V3D_LD4M_B(TT, EE, BB) hipLaunchKernelGGL((linear_decode_mxfp4_mfma_kernel<TT, EE, BB>), dim3(mblocks), dim3(512), 0, st, (const TT*)x, ldx, M, \
-                                                  (const uint8_t*)Wq, ldw, (const uint8_t*)We, lde, (const TT*)bias, (const TT*)res, ldr, (TT*)out, ldo, N, K)
-#define V3D_LD4M(TT, EE) { if (M <= 16) V3D_LD4M_B(TT, EE, 1); else V3D_LD4M_B(TT, EE, 2); }
-#define V3D_LD4M_E(TT)                                                                                \
-  switch (epilogue) {                                                                                 \
-    case F4_DEC_NONE: V3D_LD4M(TT, F4_DEC_NONE); break; case F4_DEC_BIAS: V3D_LD4M(TT, F4_DEC_BIAS); break; \
-    case F4_DEC_RES: V3D_LD4M(TT, F4_DEC_RES); break; case F4_DEC_SWIGLU: V3D_LD4M(TT, F4_DEC_SWIGLU); break; \
-    default: set_error("%s: unknown epilogue %d", who, epilogue); return V3D_E_INVALID;               \
-  }
-    if (dtype == V3D_BF16) { V3D_LD4M_E(bf16_t) } else { V3D_LD4M_E(f16_t) }
-#undef V3D_LD4M_E
-#undef V3D_LD4M
-#undef V3D_LD4M_B
-    return check_launch(who);
-  }
-  const int blocks = N / 4;
-#define V3D_LD4(TT, EE, MM)                                                                                                   \
-  hipLaunchKernelGGL((linear_decode_mxfp4_kernel<TT, EE, MM>), dim3(blocks), dim3(256), 0, st, (const TT*)x, ldx, (const uint8_t*)Wq, ldw, \
-                     (const uint8_t*)We, lde, (const TT*)bias, (const TT*)res, ldr, (TT*)out, ldo, N, K)
-#define V3D_LD4_M(TT, EE)                                                                             \
-  switch (M) { case 1: V3D_LD4(TT, EE, 1); break; case 2: V3D_LD4(TT, EE, 2); break;                  \
-               case 3: V3D_LD4(TT, EE, 3); break; default: V3D_LD4(TT, EE, 4); break; }
-#define V3D_LD4_E(TT)                                                                                 \
-  switch (epilogue) {                                                                                 \
-    case F4_DEC_NONE: V3D_LD4_M(TT, F4_DEC_NONE) break; case F4_DEC_BIAS: V3D_LD4_M(TT, F4_DEC_BIAS) break; \
-    case F4_DEC_RES: V3D_LD4_M(TT, F4_DEC_RES) break; case F4_DEC_SWIGLU: V3D_LD4_M(TT, F4_DEC_SWIGLU) break; \
-    default: set_error("%s: unknown epilogue %d", who, epilogue); return V3D_E_INVALID;               \
-  }
-  if (dtype == V3D_BF16) { V3D_LD4_E(bf16_t) } else { V3D_LD4_E(f16_t) }
-#undef V3D_LD4_E
-#undef V3D_LD4_M
-#undef V3D_LD4
-  return check_launch(who);
+  return dec_dispatch(dtype, epilogue, who, [&](auto t, auto e) {
+    using T = decltype(t);
+    constexpr int E = decltype(e)::value;
+    if (mfma_ok && M >= 2) {
+      dec_pick<1, 2>(M <= 16 ? 1 : 2, [&](auto b) {
+        hipLaunchKernelGGL((linear_decode_mxfp4_mfma_kernel<T, E, decltype(b)::value>), dim3((E == V3D_DEC_SWIGLU ? N / 2 : N) / 16), dim3(512), 0, st,
+                           (const T*)x, ldx, M, (const uint8_t*)Wq, ldw, (const uint8_t*)We, lde, (const T*)bias, (const T*)res, ldr, (T*)out, ldo,
+                           N, K);
+      });
+    } else {
+      dec_pick<1, 2, 3, 4>(M, [&](auto m) {
+        hipLaunchKernelGGL((linear_decode_mxfp4_kernel<T, E, decltype(m)::value>), dim3(N / 4), dim3(256), 0, st, (const T*)x, ldx, (const uint8_t*)Wq,
+                           ldw, (const uint8_t*)We, lde, (const T*)bias, (const T*)res, ldr, (T*)out, ldo, N, K);
+      });
+    }
+  });
 }
