@@ -1,7 +1,7 @@
 // Dense 16-bit GEMM on MFMA for the ViT / projector / LLM linears (K10-K12, K15, K17):
 //     out[M, N'] = epilogue( A[M,K] . W[N,K]^T )        A, W: K-contiguous (nn.Linear layout)
 //
-// Two tile shapes, picked per problem by a small cost model (launch_gemm):
+// Two tile shapes, picked per problem by a small cost model (gemm_plan.h):
 //   gemm_kernel         128 x 128 x 64, 4 waves (2 x 2) of 64 x 64, two workgroups per CU - fine-grained, for
 //                       shapes whose 256 x 256 tile count quantises badly against the 256 CUs;
 //   gemm256x256_kernel  256 x 256 x 64, 8 waves (2 x 4) of 128 x 64, one workgroup per CU - twice the operand
@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "v3d_common.h"
+#include "gemm_plan.h"
 #include <mutex>
 #include <unordered_map>
 #include <utility>
@@ -45,11 +46,9 @@ template <> struct Mfma16<f16_t> {
 
 template <int N> struct IntC { static constexpr int value = N; };
 
-constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int TILE_A_BYTES = BM * BK * 2;            // 16 KiB
 constexpr int STAGE_BYTES = (BM + BN) * BK * 2;      // 32 KiB
 constexpr int GEMM_LDS_BYTES = 2 * STAGE_BYTES;      // 64 KiB -> 2 workgroups per CU
-constexpr int C_ROW_BYTES = BN * 2 + 16;             // padded C-tile row in LDS
 
 struct GemmArgs {
   const void* A; const void* W; const void* bias; const void* res; void* out;
@@ -110,6 +109,85 @@ __device__ __forceinline__ void tile_of_logical(int L, int tiles_m, int tiles_n,
 
 enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU_ERF = 2, EPI_BIAS_GELU_TANH = 3, EPI_BIAS_RES = 4, EPI_RES = 5, EPI_SWIGLU = 6, EPI_BIAS_RELU = 7 };
 __host__ __device__ constexpr bool epi_has_bias(int e) { return (e >= EPI_BIAS && e <= EPI_BIAS_RES) || e == EPI_BIAS_RELU; }
+
+// ---- the C-tile epilogue of the barrier-synchronised kernels (gemm_kernel, gemm256x256_kernel, gemm_layout_kernel) ----
+// accumulators -> LDS C tile (16-bit, bias added in f32 first; rows padded by 16 bytes) -> coalesced whole row segments, with the
+// activation, the residual or SwiGLU (tile columns per 128-column group [gate64 | up64]; output width N / 2).
+// The tile is WIDTH columns of 2 x (WIDTH / 64) waves, MT x 4 accumulator tiles each.  PASSES = 1: the whole tile fits the ring
+// (128 x 128); 2: the wave rows take turns (a 256-wide C tile does not fit with its padding).  PIN holds hipcc to the register
+// budget of the kernels that were tuned with it (v3: <= 224): 1 = the packs stay in order, which bounds the live temporaries;
+// 2 = also the bias load site stays in every variant (bias is NULL for the bias-free epilogues).
+template <typename T, int EPI, int MT, int WIDTH, int THREADS, int PASSES, int PIN>
+__device__ __forceinline__ void c_tile_epilogue(const GemmArgs& p, char* smem, const f32x4 (&acc)[4][MT], int tid, int lane,
+                                                int wm, int wn, int m0, int n0, int tn) {
+  constexpr int ROWS = 2 * MT * 16 / PASSES;                               // rows per pass
+  constexpr int CROW = WIDTH * 2 + 16;
+  constexpr int TPR = EPI == EPI_SWIGLU ? WIDTH / 16 : WIDTH / 8;          // threads per row: 16 bytes of output each
+  constexpr int RPP = THREADS / TPR;                                       // rows per sweep of the workgroup
+  const T* bias = (const T*)p.bias;
+  T* out = (T*)p.out;
+#pragma unroll
+  for (int pass = 0; pass < PASSES; ++pass) {
+    if (PASSES == 1 || wm == pass) {
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) {
+        const int nl = wn * 64 + ni * 16 + 4 * (lane >> 4);
+        float bv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (epi_has_bias(EPI) || (PIN == 2 && bias != nullptr)) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) bv[r] = to_f32(bias[n0 + nl + r]);
+        }
+#pragma unroll
+        for (int mi = 0; mi < MT; ++mi) {
+          const int ml = (PASSES == 1 ? wm * MT * 16 : 0) + mi * 16 + (lane & 15);
+          uint2 pk;
+          pk.x = pack2<T>(acc[ni][mi][0] + bv[0], acc[ni][mi][1] + bv[1]);
+          pk.y = pack2<T>(acc[ni][mi][2] + bv[2], acc[ni][mi][3] + bv[3]);
+          *reinterpret_cast<uint2*>(smem + ml * CROW + nl * 2) = pk;
+          if (PIN) __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    }
+    __syncthreads();
+    auto row_out = [&](int row) {
+      const int c = tid % TPR, gm = m0 + pass * ROWS + row;
+      const char* crow = smem + row * CROW;
+      if constexpr (EPI == EPI_SWIGLU) {
+        const int grp = c >> 3, ch = c & 7;
+        const uint4 g = *reinterpret_cast<const uint4*>(crow + grp * 256 + ch * 16);
+        const uint4 u = *reinterpret_cast<const uint4*>(crow + grp * 256 + 128 + ch * 16);
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = round_to<T>(silu(vec_get<T>(g, j))) * vec_get<T>(u, j);
+        if (gm < p.M) *reinterpret_cast<uint4*>(out + (int64_t)gm * p.ldo + tn * (WIDTH / 2) + grp * 64 + ch * 8) = vec_pack<T>(v);
+      } else if (gm < p.M) {
+        uint4 cv = *reinterpret_cast<const uint4*>(crow + c * 16);
+        if (EPI == EPI_BIAS_GELU_ERF || EPI == EPI_BIAS_GELU_TANH || EPI == EPI_BIAS_RES || EPI == EPI_RES || EPI == EPI_BIAS_RELU) {
+          float v[8];
+          uint4 rr = make_uint4(0, 0, 0, 0);
+          if (EPI == EPI_BIAS_RES || EPI == EPI_RES) {
+            const int64_t rm = p.res_mod > 0 ? (gm % p.res_mod) : gm;
+            rr = *reinterpret_cast<const uint4*>((const T*)p.res + rm * p.ldr + n0 + c * 8);
+          }
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const float x = vec_get<T>(cv, j);
+            v[j] = EPI == EPI_BIAS_GELU_ERF ? gelu_erf(x) : EPI == EPI_BIAS_GELU_TANH ? gelu_tanh(x) : EPI == EPI_BIAS_RELU ? fmaxf(x, 0.f) : x + vec_get<T>(rr, j);
+          }
+          cv = vec_pack<T>(v);
+        }
+        *reinterpret_cast<uint4*>(out + (int64_t)gm * p.ldo + n0 + c * 8) = cv;
+      }
+    };
+    if constexpr (PASSES == 1) {           // the 128 x 128 kernel keeps the loads of all its rows in flight
+#pragma unroll
+      for (int i = 0; i < ROWS / RPP; ++i) row_out(tid / TPR + RPP * i);
+    } else {
+      for (int row = tid / TPR; row < ROWS; row += RPP) row_out(row);
+      __syncthreads();
+    }
+  }
+}
 
 template <typename T, int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
@@ -212,65 +290,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
 #undef V3D_WAIT
   __syncthreads();   // every wave is done with the ring before the C tile overwrites it
 
-  // ---- epilogue: accumulators -> LDS C tile (16-bit, bias added in f32 first) -> coalesced rows ----
-  const T* bias = (const T*)p.bias;
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) {
-    const int nl = wn * 64 + ni * 16 + 4 * (lane >> 4);
-    float bv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (epi_has_bias(EPI)) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) bv[r] = to_f32(bias[n0 + nl + r]);
-    }
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
-      const int ml = wm * 64 + mi * 16 + (lane & 15);
-      uint2 pk;
-      pk.x = pack2<T>(acc[ni][mi][0] + bv[0], acc[ni][mi][1] + bv[1]);
-      pk.y = pack2<T>(acc[ni][mi][2] + bv[2], acc[ni][mi][3] + bv[3]);
-      *reinterpret_cast<uint2*>(smem + ml * C_ROW_BYTES + nl * 2) = pk;
-    }
-  }
-  __syncthreads();
-
-  T* out = (T*)p.out;
-  if (EPI == EPI_SWIGLU) {
-    // tile columns [0,64) = gate_j, [64,128) = up_j of the same 64 j's; output width N/2
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = (tid >> 3) + 32 * i, ch = tid & 7;
-      const int gm = m0 + row;
-      const uint4 g = *reinterpret_cast<const uint4*>(smem + row * C_ROW_BYTES + ch * 16);
-      const uint4 u = *reinterpret_cast<const uint4*>(smem + row * C_ROW_BYTES + 128 + ch * 16);
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = round_to<T>(silu(vec_get<T>(g, j))) * vec_get<T>(u, j);
-      if (gm < p.M) *reinterpret_cast<uint4*>(out + (int64_t)gm * p.ldo + tn * 64 + ch * 8) = vec_pack<T>(v);
-    }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int row = (tid >> 4) + 16 * i, ch = tid & 15;
-    const int gm = m0 + row;
-    if (gm >= p.M) continue;
-    uint4 c = *reinterpret_cast<const uint4*>(smem + row * C_ROW_BYTES + ch * 16);
-    if (EPI == EPI_BIAS_GELU_ERF || EPI == EPI_BIAS_GELU_TANH || EPI == EPI_BIAS_RES || EPI == EPI_RES || EPI == EPI_BIAS_RELU) {
-      float v[8];
-      uint4 rr = make_uint4(0, 0, 0, 0);
-      if (EPI == EPI_BIAS_RES || EPI == EPI_RES) {
-        const int64_t rm = p.res_mod > 0 ? (gm % p.res_mod) : gm;
-        rr = *reinterpret_cast<const uint4*>((const T*)p.res + rm * p.ldr + n0 + ch * 8);
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float x = vec_get<T>(c, j);
-        v[j] = EPI == EPI_BIAS_GELU_ERF ? gelu_erf(x) : EPI == EPI_BIAS_GELU_TANH ? gelu_tanh(x) : EPI == EPI_BIAS_RELU ? fmaxf(x, 0.f) : x + vec_get<T>(rr, j);
-      }
-      c = vec_pack<T>(v);
-    }
-    *reinterpret_cast<uint4*>(out + (int64_t)gm * p.ldo + n0 + ch * 8) = c;
-  }
+  c_tile_epilogue<T, EPI, 4, BN, 256, 1, 0>(p, smem, acc, tid, lane, wm, wn, m0, n0, tn);
 }
 
 
@@ -281,7 +301,6 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
 // K-step; the fragment reads of phase p+1 are in flight under the MFMAs of phase p (two A and two B
 // register sets, counted lgkmcnt), one barrier and one 8-DMA stage per K-step on a 2-deep ring.
 // ------------------------------------------------------------------------------------------
-constexpr int B3N = 256;
 constexpr int T3_BYTES = 256 * BK * 2;                  // 32 KiB per operand tile (A tile uses BM rows of it)
 constexpr int S3_BYTES = 2 * T3_BYTES;                  // 64 KiB per stage
 constexpr int GEMM3_LDS_BYTES = 2 * S3_BYTES;           // 128 KiB
@@ -463,71 +482,7 @@ __global__ __launch_bounds__(512, 2) void gemm256x256_kernel(GemmArgs p) {
 #undef V3D_MMA
   __syncthreads();
 
-  // epilogue in two halves of WROWS rows (the whole C tile does not fit the ring with padding)
-  constexpr int C3_ROW = B3N * 2 + 16;
-  const T* bias = (const T*)p.bias;
-  T* out = (T*)p.out;
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    if (wm == half) {
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        const int nl = wn * 64 + ni * 16 + 4 * (lane >> 4);
-        float bv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (epi_has_bias(EPI) || bias != nullptr) {   // (bias is NULL for the bias-free epilogues; keeping the
-#pragma unroll                                          //  load site in every variant keeps hipcc at <= 224 VGPRs)
-          for (int r = 0; r < 4; ++r) bv[r] = to_f32(bias[n0 + nl + r]);
-        }
-#pragma unroll
-        for (int mi = 0; mi < MT; ++mi) {
-          const int ml = mi * 16 + (lane & 15);
-          uint2 pk;
-          pk.x = pack2<T>(acc[ni][mi][0] + bv[0], acc[ni][mi][1] + bv[1]);
-          pk.y = pack2<T>(acc[ni][mi][2] + bv[2], acc[ni][mi][3] + bv[3]);
-          *reinterpret_cast<uint2*>(smem + ml * C3_ROW + nl * 2) = pk;
-          __builtin_amdgcn_sched_barrier(0);      // keep the packs in order: bounds the live temporaries (<= 224 VGPRs)
-        }
-      }
-    }
-    __syncthreads();
-    if (EPI == EPI_SWIGLU) {
-      // tile columns: per 128-column group [gate64 | up64]; two groups per tile -> 128 output columns
-      for (int row = tid >> 4; row < WROWS; row += 32) {
-        const int c16 = tid & 15, grp = c16 >> 3, ch = c16 & 7;
-        const int gm = m0 + half * WROWS + row;
-        const uint4 g = *reinterpret_cast<const uint4*>(smem + row * C3_ROW + grp * 256 + ch * 16);
-        const uint4 u = *reinterpret_cast<const uint4*>(smem + row * C3_ROW + grp * 256 + 128 + ch * 16);
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = round_to<T>(silu(vec_get<T>(g, j))) * vec_get<T>(u, j);
-        if (gm < p.M) *reinterpret_cast<uint4*>(out + (int64_t)gm * p.ldo + tn * 128 + grp * 64 + ch * 8) = vec_pack<T>(v);
-      }
-    } else {
-      for (int row = tid >> 5; row < WROWS; row += 16) {
-        const int ch = tid & 31;
-        const int gm = m0 + half * WROWS + row;
-        if (gm < p.M) {
-          uint4 c = *reinterpret_cast<const uint4*>(smem + row * C3_ROW + ch * 16);
-          if (EPI == EPI_BIAS_GELU_ERF || EPI == EPI_BIAS_GELU_TANH || EPI == EPI_BIAS_RES || EPI == EPI_RES || EPI == EPI_BIAS_RELU) {
-            float v[8];
-            uint4 rr = make_uint4(0, 0, 0, 0);
-            if (EPI == EPI_BIAS_RES || EPI == EPI_RES) {
-              const int64_t rm = p.res_mod > 0 ? (gm % p.res_mod) : gm;
-              rr = *reinterpret_cast<const uint4*>((const T*)p.res + rm * p.ldr + n0 + ch * 8);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              const float x = vec_get<T>(c, j);
-              v[j] = EPI == EPI_BIAS_GELU_ERF ? gelu_erf(x) : EPI == EPI_BIAS_GELU_TANH ? gelu_tanh(x) : EPI == EPI_BIAS_RELU ? fmaxf(x, 0.f) : x + vec_get<T>(rr, j);
-            }
-            c = vec_pack<T>(v);
-          }
-          *reinterpret_cast<uint4*>(out + (int64_t)gm * p.ldo + n0 + ch * 8) = c;
-        }
-      }
-    }
-    __syncthreads();
-  }
+  c_tile_epilogue<T, EPI, MT, B3N, 512, 2, 2>(p, smem, acc, tid, lane, wm, wn, m0, n0, tn);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1142,6 +1097,22 @@ static int gemm_dma_mode() {   // -1 = auto, 0 / 1 = force (A/B runs)
   return v;
 }
 
+// the runtime epilogue code as a compile-time one: f(IntC<E>{})
+template <typename F>
+static int with_epilogue(int epi, F&& f) {
+  switch (epi) {
+    case EPI_NONE: return f(IntC<EPI_NONE>{});
+    case EPI_BIAS: return f(IntC<EPI_BIAS>{});
+    case EPI_BIAS_GELU_ERF: return f(IntC<EPI_BIAS_GELU_ERF>{});
+    case EPI_BIAS_GELU_TANH: return f(IntC<EPI_BIAS_GELU_TANH>{});
+    case EPI_BIAS_RES: return f(IntC<EPI_BIAS_RES>{});
+    case EPI_RES: return f(IntC<EPI_RES>{});
+    case EPI_SWIGLU: return f(IntC<EPI_SWIGLU>{});
+    case EPI_BIAS_RELU: return f(IntC<EPI_BIAS_RELU>{});
+    default: set_error("v3d_gemm: unknown epilogue %d", epi); return V3D_E_INVALID;
+  }
+}
+
 template <typename T, int MT>
 static int launch_gemm256x256(GemmArgs p, int epi, hipStream_t st) {
   constexpr int BM = MT * 32;
@@ -1149,30 +1120,9 @@ static int launch_gemm256x256(GemmArgs p, int epi, hipStream_t st) {
   p.dma_late = gemm_dma_mode() > 0 ? 1 : 0;
   p.tiles_m = (p.M + BM - 1) / BM;
   p.tiles_n = p.N / B3N;
-#define V3D_GEMM3_CASE(E)                                                                                 \
-  case E: {                                                                                               \
-    auto k = gemm256x256_kernel<T, E, MT>;                                                                \
-    static bool attr_done = false;                                                                        \
-    if (!attr_done) {                                                                                     \
-      hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM3_LDS_BYTES); \
-      if (e != hipSuccess) { set_error("v3d_gemm: LDS attribute: %s", hipGetErrorString(e)); return V3D_E_LAUNCH; } \
-      attr_done = true;                                                                                   \
-    }                                                                                                     \
-    hipLaunchKernelGGL(k, dim3(p.tiles_m * p.tiles_n), dim3(512), GEMM3_LDS_BYTES, st, p);                \
-  } break;
-  switch (epi) {
-    V3D_GEMM3_CASE(EPI_NONE)
-    V3D_GEMM3_CASE(EPI_BIAS)
-    V3D_GEMM3_CASE(EPI_BIAS_GELU_ERF)
-    V3D_GEMM3_CASE(EPI_BIAS_GELU_TANH)
-    V3D_GEMM3_CASE(EPI_BIAS_RES)
-    V3D_GEMM3_CASE(EPI_RES)
-    V3D_GEMM3_CASE(EPI_SWIGLU)
-    V3D_GEMM3_CASE(EPI_BIAS_RELU)
-    default: set_error("v3d_gemm: unknown epilogue %d", epi); return V3D_E_INVALID;
-  }
-#undef V3D_GEMM3_CASE
-  return check_launch("v3d_gemm (256-wide)");
+  return with_epilogue(epi, [&](auto e) {
+    return launch_big_lds<gemm256x256_kernel<T, decltype(e)::value, MT>, GEMM3_LDS_BYTES, 512>(p, p.tiles_m * p.tiles_n, "v3d_gemm (256-wide)", st);
+  });
 }
 
 static int gemm_pp_mode() {   // 1 (default) = ping-pong v4 for the 256 x 256 tile, 0 = the v3 kernel; read per call so that a
@@ -1199,26 +1149,6 @@ static int gemm_sk_mode() {
   const char* e = getenv("V3D_GEMM_STREAMK");
   return e ? atoi(e) : 1;
 }
-// Legal: grid a multiple of 8 (the XCD-major order), an even number of K-steps (granule = 2) with at least two granules per chunk,
-// and the tiles left after the whole-tile rounds fit the grid at least twice.  Returns the whole-tile rounds (or -1) and the split.
-static int sk_plan(int n_tiles, int grid, int nt, int* split) {
-  *split = 1;
-  if (grid < 8 || (grid & 7) || (nt & 1)) return -1;
-  const int dp = n_tiles / grid, rest = n_tiles - dp * grid;      // (dp = 0: fewer tiles than workgroups - the whole launch is the tail)
-  if (rest == 0) return -1;                  // whole rounds only
-  int sp = grid / rest;
-  sp = sp > 4 ? 4 : sp;
-  if (sp < 2 || (nt >> 1) < 2 * sp) return -1;
-  *split = sp;
-  return dp;
-}
-static bool sk_pays(int n_tiles, int grid, int nt) {           // the time model of launch_gemm: whole rounds vs whole rounds + split tail
-  int sp = 1;
-  const int dp = sk_plan(n_tiles, grid, nt, &sp);
-  if (dp < 0) return false;
-  const double ks = (double)nt, round = 8.0 + 1.263 * ks;
-  return dp * round + (dp > 0 ? 5.0 : 0.0) + 22.0 + (dp > 0 ? 1.7 : 1.3) * ks / sp + 40.0 < (double)((n_tiles + grid - 1) / grid) * round;
-}
 struct SkWorkspace { float* ws = nullptr; unsigned* flags = nullptr; unsigned epoch = 0; int slots = 0; };
 // One workspace per stream (launches on one stream are ordered; two streams must not share accumulator images).  Allocated on
 // first use, never during stream capture (the caller then gets the plain walk).
@@ -1242,57 +1172,18 @@ static SkWorkspace* sk_workspace(hipStream_t st, int grid, unsigned* epoch) {   
   return &w;
 }
 
+// in the tail launch a chunk-0 workgroup waits (unbounded) for flags its partner chunks raise.  That is deadlock-free
+// only while every workgroup of the launch becomes resident - true for ONE tail launch on the chip (grid <= one workgroup per CU),
+// not for two that interleave their dispatch (two streams): waiting chunk-0 workgroups of both could fill an XCD whose
+// writers then never start.  So tail launches of this process are CHAINED: each waits for the previous one's completion event,
+// whatever stream it was on.  (Two PROCESSES sharing one card - the gloo rehearsals - run with V3D_GEMM_STREAMK=0.)
+struct TailChain { std::mutex mu; hipEvent_t done = nullptr; hipStream_t last = nullptr; bool recorded = false; };
+static TailChain g_tail_chain;
+
+// One launch of prepared arguments on `grid` workgroups; a split-K tail (p.sk_dp >= 0) takes its place in the chain.
 template <typename T, int MT>
-static int launch_gemm256pp(GemmArgs p, int epi, hipStream_t st, int sk_allow = -1) {   // sk_allow: -1 decide here (forced tile), 0 / 1 = the caller's model decided
-  p.tiles_m = (p.M + MT * 32 - 1) / (MT * 32);
-  p.tiles_n = p.N / B3N;
-  const bool part = sk_allow == -2;                                 // a launch over the tile range the caller set (no split of its own)
-  if (!part) { p.tile_base = 0; p.tile_count = 0; }
-  const int n_tiles = part ? p.tile_count : p.tiles_m * p.tiles_n;
-  int grid = n_tiles < pp_slots() ? n_tiles : pp_slots();           // persistent: one workgroup per CU walks its tiles
-  { const char* e = getenv("V3D_GEMM_SKEW"); p.skew = e ? atoi(e) : 0; }
-  if (n_tiles <= grid) p.skew = 0;                                  // a single round: nothing to spread
-  p.sk_dp = -1; p.sk_split = 1; p.sk_ws = nullptr; p.sk_flags = nullptr; p.sk_epoch = 0;
-  {
-    int split = 1;
-    const int slots = pp_slots() & ~7;
-    const int mode = gemm_sk_mode(), dp = sk_plan(n_tiles, slots, p.K / BK, &split);
-    if (!part && MT == 8 && mode != 0 && dp >= 0 && (mode == 2 || (sk_allow < 0 ? sk_pays(n_tiles, slots, p.K / BK) : sk_allow != 0))) {
-      unsigned epoch = 0;
-      if (SkWorkspace* w = sk_workspace(st, slots, &epoch)) {
-        // The whole-tile rounds go out as a launch of their own with the instantiation that has no exchange code (no spills), the
-        // tail as a second launch: its chunks then all start together and stay in lock step (tail K-steps 1.3 us instead of 1.7).
-        if (dp > 0) {
-          GemmArgs pw = p;
-          pw.tile_base = 0; pw.tile_count = dp * slots;
-          const int rc = launch_gemm256pp<T, MT>(pw, epi, st, -2);
-          if (rc != V3D_OK) return rc;
-          p.tile_base = dp * slots; p.tile_count = n_tiles - dp * slots;
-        }
-        p.sk_dp = 0; p.sk_split = split; p.sk_ws = w->ws; p.sk_flags = w->flags; p.sk_epoch = epoch;
-        p.skew = 0;
-        grid = slots;                                               // (also when n_tiles < slots: the chunks fill the chip)
-      }
-    }
-  }
-#define V3D_GEMM4_LAUNCH(E, SKT)                                                                          \
-  {                                                                                                       \
-    auto k = gemm256pp_kernel<T, E, MT, SKT>;                                                             \
-    static bool attr_done = false;                                                                        \
-    if (!attr_done) {                                                                                     \
-      hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES); \
-      if (e != hipSuccess) { set_error("v3d_gemm: LDS attribute: %s", hipGetErrorString(e)); return V3D_E_LAUNCH; } \
-      attr_done = true;                                                                                   \
-    }                                                                                                     \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(512), PP_LDS_BYTES, st, p);                                    \
-  }
-  // in the tail launch a chunk-0 workgroup waits (unbounded) for flags its partner chunks raise.  That is deadlock-free
-  // only while every workgroup of the launch becomes resident - true for ONE tail launch on the chip (grid <= one workgroup per CU),
-  // not for two that interleave their dispatch (two streams): waiting chunk-0 workgroups of both could fill an XCD whose
-  // writers then never start.  So tail launches of this process are CHAINED: each waits for the previous one's completion event,
-  // whatever stream it was on.  (Two PROCESSES sharing one card - the gloo rehearsals - run with V3D_GEMM_STREAMK=0.)
-  struct TailChain { std::mutex mu; hipEvent_t done = nullptr; hipStream_t last = nullptr; bool recorded = false; };
-  static TailChain chain;
+static int launch_pp_raw(const GemmArgs& p, int grid, int epi, hipStream_t st) {
+  TailChain& chain = g_tail_chain;
   const bool is_tail = p.sk_dp >= 0;
   std::unique_lock<std::mutex> tail_lock(chain.mu, std::defer_lock);
   if (is_tail) {
@@ -1300,25 +1191,15 @@ static int launch_gemm256pp(GemmArgs p, int epi, hipStream_t st, int sk_allow = 
     if (!chain.done && hipEventCreateWithFlags(&chain.done, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); chain.done = nullptr; }
     if (chain.done && chain.recorded && chain.last != st) (void)hipStreamWaitEvent(st, chain.done, 0);
   }
-#define V3D_GEMM4_CASE(E)                                                                                 \
-  case E: {                                                                                               \
-    if constexpr (MT == 8) { if (p.sk_dp >= 0) V3D_GEMM4_LAUNCH(E, true) else V3D_GEMM4_LAUNCH(E, false) } \
-    else V3D_GEMM4_LAUNCH(E, false)                                                                        \
-  } break;
-  switch (epi) {
-    V3D_GEMM4_CASE(EPI_NONE)
-    V3D_GEMM4_CASE(EPI_BIAS)
-    V3D_GEMM4_CASE(EPI_BIAS_GELU_ERF)
-    V3D_GEMM4_CASE(EPI_BIAS_GELU_TANH)
-    V3D_GEMM4_CASE(EPI_BIAS_RES)
-    V3D_GEMM4_CASE(EPI_RES)
-    V3D_GEMM4_CASE(EPI_SWIGLU)
-    V3D_GEMM4_CASE(EPI_BIAS_RELU)
-    default: set_error("v3d_gemm: unknown epilogue %d", epi); return V3D_E_INVALID;
-  }
-#undef V3D_GEMM4_CASE
-#undef V3D_GEMM4_LAUNCH
-  if (is_tail && chain.done) {
+  const int rc = with_epilogue(epi, [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    const char* who = "v3d_gemm (256-wide, ping-pong)";
+    if constexpr (MT == 8) {               // (only the 256-row tile has the instantiation with the exchange code)
+      if (is_tail) return launch_big_lds<gemm256pp_kernel<T, E, MT, true>, PP_LDS_BYTES, 512>(p, grid, who, st);
+    }
+    return launch_big_lds<gemm256pp_kernel<T, E, MT, false>, PP_LDS_BYTES, 512>(p, grid, who, st);
+  });
+  if (rc == V3D_OK && is_tail && chain.done) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone && hipEventRecord(chain.done, st) == hipSuccess) {
       chain.recorded = true; chain.last = st;
@@ -1326,44 +1207,45 @@ static int launch_gemm256pp(GemmArgs p, int epi, hipStream_t st, int sk_allow = 
       (void)hipGetLastError();
     }
   }
-  return check_launch("v3d_gemm (256-wide, ping-pong)");
+  return rc;
 }
 
-// Tile choice (speed only), from a time model fitted on MI355X to the path's shapes (tools/time_gemm_ab.py; microseconds):
-//   a kernel takes  rounds x (fixed + K-steps x per-step),  rounds = ceil(tiles / workgroup slots of the chip)
-//   256 x 256 ping-pong (256 slots): fixed 8 (epilogue, rendezvous, first DMA latency; 13 with SwiGLU), 1.26 per K-step
-//   192 x 256 ping-pong (256 slots): fixed 4.5, 1.22 per K-step   (3/4 of the tile at the same step time: it only wins where
-//                                    256-row tiles quantise badly against the 256 CUs, e.g. M = 6794, N = 3584, K = 3584)
-//   128 x 128           (512 slots): fixed 1, 0.98 per K-step     (many small tiles: small M, or N % 256 != 0)
-//   256 x 256 with the split-K tail: whole rounds as above (a launch of their own) + 5 for the second launch + one round of
-//                                    (22 + step x K-steps / split + 40 for the exchange),
-//                                    step 1.3 when the launch is only the tail, 1.7 behind whole rounds (measured: 6794 x 3584 x 18944
-//                                    780 -> 685 us, 960 x 3584 x 18944 330 -> 152 us; no gain at K = 3584)
-struct GemmPlan { int kernel; int sk; int dp; int split; int tiles; };    // kernel: 1 = 128 x 128, 2 = 256 x 256, 3 = 192 x 256 (2, 3: ping-pong or v3)
-static GemmPlan gemm_plan(int M, int N, int K, int slots, int var, bool pp_on, int sk_mode) {
-  GemmPlan g = {1, 0, -1, 1, ((M + BM - 1) / BM) * (N / BN)};
-  if (N % B3N != 0 || var == 1) return g;
-  const double ks = (double)(K / BK);
-  const int tiles256 = ((M + 255) / 256) * (N / B3N), tiles192 = ((M + 191) / 192) * (N / B3N);
-  const bool pp = pp_on && K >= 2 * BK;
-  double t256 = (double)((tiles256 + 255) / 256) * (pp ? 8.0 + 1.263 * ks : 9.0 + 1.36 * ks);
-  const double t192 = (double)((tiles192 + 255) / 256) * (pp ? 4.5 + 1.2225 * ks : 2.0 + 1.32 * ks);
-  const int r1 = (g.tiles + 511 - 25) / 512;                     // (a last round under 5 % full is not felt)
-  const double t1 = (double)(r1 > 0 ? r1 : 1) * (1.0 + 0.98 * ks);
-  int sk_use = 0, sp = 1, dp = -1;
-  if (pp && sk_mode != 0) {
-    dp = sk_plan(tiles256, slots & ~7, K / BK, &sp);
-    if (dp >= 0) {
-      const double tsk = dp * (8.0 + 1.263 * ks) + (dp > 0 ? 5.0 : 0.0) + 22.0 + (dp > 0 ? 1.7 : 1.3) * ks / sp + 40.0;
-      const double best = t256 < t192 ? (t256 < t1 ? t256 : t1) : (t192 < t1 ? t192 : t1);
-      if (tsk < 0.98 * best || sk_mode == 2) { t256 = tsk < t256 ? tsk : t256; sk_use = 1; }    // (a 2 % margin: the model is coarse)
-    }
+// The plain persistent walk over the n_tiles logical tiles from p.tile_base: one workgroup per CU (or per tile) walks its tiles.
+template <typename T, int MT>
+static int launch_pp_walk(GemmArgs p, int n_tiles, int epi, hipStream_t st) {
+  const int grid = n_tiles < pp_slots() ? n_tiles : pp_slots();
+  const char* e = getenv("V3D_GEMM_SKEW");
+  p.skew = e && n_tiles > grid ? atoi(e) : 0;                         // (a single round: nothing to spread)
+  return launch_pp_raw<T, MT>(p, grid, epi, st);
+}
+
+enum class SplitK { Decide, Off, On };    // the split-K tail: by this launcher's own rule (a forced tile), or as the caller's plan decided
+
+template <typename T, int MT>
+static int launch_gemm256pp(GemmArgs p, int epi, hipStream_t st, SplitK sk) {
+  p.tiles_m = (p.M + MT * 32 - 1) / (MT * 32);
+  p.tiles_n = p.N / B3N;
+  p.tile_base = 0; p.tile_count = 0;
+  p.sk_dp = -1; p.sk_split = 1; p.sk_ws = nullptr; p.sk_flags = nullptr; p.sk_epoch = 0;
+  const int n_tiles = p.tiles_m * p.tiles_n, slots = pp_slots() & ~7, nt = p.K / BK;
+  int split = 1;
+  const int mode = gemm_sk_mode(), dp = sk_plan(n_tiles, slots, nt, &split);
+  const bool want = MT == 8 && mode != 0 && dp >= 0 && (mode == 2 || (sk == SplitK::Decide ? sk_pays(n_tiles, slots, nt) : sk == SplitK::On));
+  unsigned epoch = 0;
+  SkWorkspace* w = want ? sk_workspace(st, slots, &epoch) : nullptr;
+  if (!w) return launch_pp_walk<T, MT>(p, n_tiles, epi, st);
+  // The whole-tile rounds go out as a launch of their own with the instantiation that has no exchange code (no spills), the
+  // tail as a second launch: its chunks then all start together and stay in lock step (tail K-steps 1.3 us instead of 1.7).
+  if (dp > 0) {
+    GemmArgs pw = p;
+    pw.tile_count = dp * slots;
+    const int rc = launch_pp_walk<T, MT>(pw, dp * slots, epi, st);
+    if (rc != V3D_OK) return rc;
+    p.tile_base = dp * slots; p.tile_count = n_tiles - dp * slots;
   }
-  if (var == 4) { g.kernel = 3; g.tiles = tiles192; g.sk = -1; return g; }       // forced tiles decide the split themselves (sk = -1)
-  if (var == 3) { g.kernel = 2; g.tiles = tiles256; g.sk = -1; return g; }
-  if (t192 < t256 && t192 < t1) { g.kernel = 3; g.tiles = tiles192; return g; }
-  if (t256 < t1) { g.kernel = 2; g.tiles = tiles256; g.sk = sk_use; if (sk_use) { g.dp = dp; g.split = sp; } return g; }
-  return g;
+  p.sk_dp = 0; p.sk_split = split; p.sk_ws = w->ws; p.sk_flags = w->flags; p.sk_epoch = epoch;
+  p.skew = 0;
+  return launch_pp_raw<T, MT>(p, slots, epi, st);                    // (also when n_tiles < slots: the chunks fill the chip)
 }
 
 template <typename T>
@@ -1371,32 +1253,12 @@ static int launch_gemm(const GemmArgs& p, int epi, hipStream_t st) {
   const bool pp_on = gemm_pp_mode() != 0;
   const GemmPlan g = gemm_plan(p.M, p.N, p.K, pp_slots(), gemm_variant(), pp_on, gemm_sk_mode());
   const bool pp = pp_on && p.K >= 2 * BK;
-  if (g.kernel == 3) return pp ? launch_gemm256pp<T, 6>(p, epi, st, g.sk < 0 ? -1 : 0) : launch_gemm256x256<T, 6>(p, epi, st);
-  if (g.kernel == 2) return pp ? launch_gemm256pp<T, 8>(p, epi, st, g.sk) : launch_gemm256x256<T, 8>(p, epi, st);
-#define V3D_GEMM_CASE(E)                                                                                  \
-  case E: {                                                                                               \
-    auto k = gemm_kernel<T, E>;                                                                           \
-    static bool attr_done = false;                                                                        \
-    if (!attr_done) {                                                                                     \
-      hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES); \
-      if (e != hipSuccess) { set_error("v3d_gemm: LDS attribute: %s", hipGetErrorString(e)); return V3D_E_LAUNCH; } \
-      attr_done = true;                                                                                   \
-    }                                                                                                     \
-    hipLaunchKernelGGL(k, dim3(p.tiles_m * p.tiles_n), dim3(256), GEMM_LDS_BYTES, st, p);                 \
-  } break;
-  switch (epi) {
-    V3D_GEMM_CASE(EPI_NONE)
-    V3D_GEMM_CASE(EPI_BIAS)
-    V3D_GEMM_CASE(EPI_BIAS_GELU_ERF)
-    V3D_GEMM_CASE(EPI_BIAS_GELU_TANH)
-    V3D_GEMM_CASE(EPI_BIAS_RES)
-    V3D_GEMM_CASE(EPI_RES)
-    V3D_GEMM_CASE(EPI_SWIGLU)
-    V3D_GEMM_CASE(EPI_BIAS_RELU)
-    default: set_error("v3d_gemm: unknown epilogue %d", epi); return V3D_E_INVALID;
-  }
-#undef V3D_GEMM_CASE
-  return check_launch("v3d_gemm");
+  const SplitK sk = g.sk < 0 ? SplitK::Decide : g.sk ? SplitK::On : SplitK::Off;
+  if (g.kernel == 3) return pp ? launch_gemm256pp<T, 6>(p, epi, st, sk) : launch_gemm256x256<T, 6>(p, epi, st);
+  if (g.kernel == 2) return pp ? launch_gemm256pp<T, 8>(p, epi, st, sk) : launch_gemm256x256<T, 8>(p, epi, st);
+  return with_epilogue(epi, [&](auto e) {
+    return launch_big_lds<gemm_kernel<T, decltype(e)::value>, GEMM_LDS_BYTES, 256>(p, p.tiles_m * p.tiles_n, "v3d_gemm", st);
+  });
 }
 
 template <typename T>
@@ -1625,53 +1487,7 @@ __global__ __launch_bounds__(BIG ? 512 : 256, 2) void gemm_layout_kernel(GemmArg
 #undef V3D_LMMA
   __syncthreads();
 
-  // ---- epilogue (the code of gemm256x256_kernel): two halves of WROWS rows through a padded LDS C tile, whole row segments out ----
-  constexpr int CROW = LBN * 2 + 16;
-  constexpr int TPR = LBN / 8;                            // threads per C row (16 bytes each)
-  constexpr int RPP = (BIG ? 512 : 256) / TPR;            // rows per pass
-  const T* bias = (const T*)p.bias;
-  T* out = (T*)p.out;
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    if (wm == half) {
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        const int nl = wn * 64 + ni * 16 + 4 * (lane >> 4);
-        float bv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (epi_has_bias(EPI)) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) bv[r] = to_f32(bias[n0 + nl + r]);
-        }
-#pragma unroll
-        for (int mi = 0; mi < MT; ++mi) {
-          const int ml = mi * 16 + (lane & 15);
-          uint2 pk;
-          pk.x = pack2<T>(acc[ni][mi][0] + bv[0], acc[ni][mi][1] + bv[1]);
-          pk.y = pack2<T>(acc[ni][mi][2] + bv[2], acc[ni][mi][3] + bv[3]);
-          *reinterpret_cast<uint2*>(smem + ml * CROW + nl * 2) = pk;
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    }
-    __syncthreads();
-    for (int row = tid / TPR; row < WROWS; row += RPP) {
-      const int ch = tid % TPR;
-      const int gm = m0 + half * WROWS + row;
-      if (gm < p.M) {
-        uint4 c = *reinterpret_cast<const uint4*>(smem + row * CROW + ch * 16);
-        if (EPI == EPI_BIAS_RES || EPI == EPI_RES) {
-          float v[8];
-          const int64_t rm = p.res_mod > 0 ? (gm % p.res_mod) : gm;
-          const uint4 rr = *reinterpret_cast<const uint4*>((const T*)p.res + rm * p.ldr + n0 + ch * 8);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = vec_get<T>(c, j) + vec_get<T>(rr, j);
-          c = vec_pack<T>(v);
-        }
-        *reinterpret_cast<uint4*>(out + (int64_t)gm * p.ldo + n0 + ch * 8) = c;
-      }
-    }
-    __syncthreads();
-  }
+  c_tile_epilogue<T, EPI, MT, LBN, BIG ? 512 : 256, 2, 1>(p, smem, acc, tid, lane, wm, wn, m0, n0, tn);
 }
 
 static int gemm_layout_tile() {   // 0 = by the cost model, 128 / 256 = force that tile form; read per call (tests, A/B runs)
@@ -1679,29 +1495,12 @@ static int gemm_layout_tile() {   // 0 = by the cost model, 128 / 256 = force th
   return e ? atoi(e) : 0;
 }
 
-// Tile form by gemm_plan's constants for the 128 x 128 kernel and the 256 x 256 v3 kernel (the schedule this one shares).
-static bool gemm_layout_big(int M, int N, int K) {
-  if (N % B3N != 0) return false;
-  const double ks = (double)((K + BK - 1) / BK);
-  const int tiles256 = ((M + 255) / 256) * (N / B3N), tiles128 = ((M + BM - 1) / BM) * (N / BN);
-  const int r1 = (tiles128 + 511 - 25) / 512;
-  return (double)((tiles256 + 255) / 256) * (9.0 + 1.36 * ks) < (double)(r1 > 0 ? r1 : 1) * (1.0 + 0.98 * ks);
-}
-
 template <typename T, int EPI, bool AKM, bool BKM, bool BIG>
 static int launch_gemm_layout_one(GemmArgs p, hipStream_t st) {
   constexpr int LBM = BIG ? 256 : 128, LBN = BIG ? 256 : 128, LDS = BIG ? GEMM3_LDS_BYTES : GEMM_LDS_BYTES;
   p.tiles_m = (p.M + LBM - 1) / LBM;
   p.tiles_n = p.N / LBN;
-  auto k = gemm_layout_kernel<T, EPI, AKM, BKM, BIG>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) { set_error("v3d_gemm_layout: LDS attribute: %s", hipGetErrorString(e)); return V3D_E_LAUNCH; }
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(k, dim3(p.tiles_m * p.tiles_n), dim3(BIG ? 512 : 256), LDS, st, p);
-  return check_launch("v3d_gemm_layout");
+  return launch_big_lds<gemm_layout_kernel<T, EPI, AKM, BKM, BIG>, LDS, BIG ? 512 : 256>(p, p.tiles_m * p.tiles_n, "v3d_gemm_layout", st);
 }
 
 template <typename T, int EPI>
@@ -1719,15 +1518,6 @@ static int launch_gemm_layout(const GemmArgs& p, bool akm, bool bkm, bool big, h
 }  // namespace v3d
 
 using namespace v3d;
-
-extern "C" int v3d_gemm_plan_host(int M, int N, int K, int slots, int* kernel, int* tiles, int* dp, int* split) {
-  V3D_REQUIRE(M > 0 && N > 0 && K > 0 && N % BN == 0 && K % BK == 0 && slots > 0, "v3d_gemm_plan_host: bad shape");
-  V3D_REQUIRE(kernel && tiles && dp && split, "v3d_gemm_plan_host: null pointer");
-  if (M <= 8) { *kernel = 0; *tiles = 0; *dp = -1; *split = 1; return V3D_OK; }
-  const GemmPlan g = gemm_plan(M, N, K, slots, 0, true, 1);
-  *kernel = g.kernel; *tiles = g.tiles; *dp = g.sk > 0 ? g.dp : -1; *split = g.sk > 0 ? g.split : 1;
-  return V3D_OK;
-}
 
 extern "C" int v3d_gemm(const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, const void* res,
                         int64_t ldr, int res_mod, void* out, int64_t ldo, int M, int N, int K, int dtype, int epilogue,

@@ -370,18 +370,6 @@ static int q8_validate(const char* who, const Q8GemmArgs& p, bool fmt_ptrs, bool
   return V3D_OK;
 }
 
-template <void (*KERNEL)(Q8GemmArgs), int LDS>
-static int q8_launch_kernel(const Q8GemmArgs& p, const char* who, hipStream_t st) {
-  static bool attr_done = false;                         // per instantiated kernel
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) { set_error("%s: LDS attribute: %s", who, hipGetErrorString(e)); return V3D_E_LAUNCH; }
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(KERNEL, dim3(p.tiles_m * p.tiles_n), dim3(512), LDS, st, p);
-  return check_launch(who);
-}
-
 // NONE, BIAS, RES, SWIGLU = the four instantiations of one entry point for one output type
 template <int LDS, void (*NONE)(Q8GemmArgs), void (*BIAS)(Q8GemmArgs), void (*RES)(Q8GemmArgs), void (*SWIGLU)(Q8GemmArgs)>
 static int q8_launch(Q8GemmArgs p, int epi, const char* who, hipStream_t st) {
@@ -390,10 +378,10 @@ static int q8_launch(Q8GemmArgs p, int epi, const char* who, hipStream_t st) {
   p.bias = epi == Q8_EPI_BIAS ? p.bias : nullptr;
   p.res = epi == Q8_EPI_RES ? p.res : nullptr;
   switch (epi) {
-    case Q8_EPI_NONE: return q8_launch_kernel<NONE, LDS>(p, who, st);
-    case Q8_EPI_BIAS: return q8_launch_kernel<BIAS, LDS>(p, who, st);
-    case Q8_EPI_RES: return q8_launch_kernel<RES, LDS>(p, who, st);
-    case Q8_EPI_SWIGLU: return q8_launch_kernel<SWIGLU, LDS>(p, who, st);
+    case Q8_EPI_NONE: return launch_big_lds<NONE, LDS, 512>(p, p.tiles_m * p.tiles_n, who, st);
+    case Q8_EPI_BIAS: return launch_big_lds<BIAS, LDS, 512>(p, p.tiles_m * p.tiles_n, who, st);
+    case Q8_EPI_RES: return launch_big_lds<RES, LDS, 512>(p, p.tiles_m * p.tiles_n, who, st);
+    case Q8_EPI_SWIGLU: return launch_big_lds<SWIGLU, LDS, 512>(p, p.tiles_m * p.tiles_n, who, st);
     default: set_error("%s: epilogue %d unsupported (NONE, BIAS, RES, SWIGLU)", who, epi); return V3D_E_INVALID;
   }
 }

@@ -1,5 +1,5 @@
 // Host side of the C ABI: error reporting and the host-only helpers (frame sampling,
-// greedy max-coverage frame selection, the beam-search step's twin, the sampler's twin, the logits processors' twin).
+// greedy max-coverage frame selection, the beam-search step's twin, the sampler's twin, the logits processors' twin, the GEMM planner).
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -12,6 +12,7 @@
 #include "beam_step.h"
 #include "sample_rule.h"
 #include "logits_rule.h"
+#include "gemm_plan.h"
 
 namespace v3d {
 
@@ -253,5 +254,22 @@ extern "C" int v3d_philox4x32_10_host(const uint32_t* counter, const uint32_t* k
   }
   const v3d::Philox4 w = v3d::philox4x32_10(counter[0], counter[1], counter[2], counter[3], key[0], key[1]);
   for (int i = 0; i < 4; ++i) out[i] = w.w[i];
+  return V3D_OK;
+}
+
+// The plan v3d_gemm makes for a shape on a chip of `slots` CUs at the default switches (gemm_plan.h): kernel 0 = skinny,
+// 1 = 128 x 128, 2 = 256 x 256, 3 = 192 x 256; dp / split: the split-K tail's whole-tile rounds and K-chunks (-1 / 1: no tail)
+extern "C" int v3d_gemm_plan_host(int M, int N, int K, int slots, int* kernel, int* tiles, int* dp, int* split) {
+  if (!(M > 0 && N > 0 && K > 0 && N % v3d::BN == 0 && K % v3d::BK == 0 && slots > 0)) {
+    v3d::set_error("v3d_gemm_plan_host: bad shape");
+    return V3D_E_INVALID;
+  }
+  if (!(kernel && tiles && dp && split)) {
+    v3d::set_error("v3d_gemm_plan_host: null pointer");
+    return V3D_E_INVALID;
+  }
+  if (M <= 8) { *kernel = 0; *tiles = 0; *dp = -1; *split = 1; return V3D_OK; }
+  const v3d::GemmPlan g = v3d::gemm_plan(M, N, K, slots, 0, true, 1);
+  *kernel = g.kernel; *tiles = g.tiles; *dp = g.sk > 0 ? g.dp : -1; *split = g.sk > 0 ? g.split : 1;
   return V3D_OK;
 }

@@ -214,6 +214,55 @@ int main() {
       CHECK(v3d_logits_process_rows_host(x.data(), ldx, M, V, dtype, hist, ld, L, 1.f, 0, 1, nullptr, 3) == V3D_E_INVALID);
     }
   }
+  // the GEMM planner (gemm_plan.h): the plans of the path's shapes on a 256-CU chip, then a sweep that holds every split-K plan to
+  // what the kernel needs - the item list is rebuilt the way gemm256pp_kernel walks it (XCD-major id g = xcd * wx + idx, item
+  // g = (chunk g / T, tile g mod T)): each K-chunk has a workgroup, each chunk-0 workgroup finds its partners by the kernel's formula
+  {
+    struct P { int kernel, tiles, dp, split; };
+    auto plan = [](int M, int N, int K, int slots, P* p) { return v3d_gemm_plan_host(M, N, K, slots, &p->kernel, &p->tiles, &p->dp, &p->split); };
+    auto is = [](const P& p, int k, int t, int d, int s) { return p.kernel == k && p.tiles == t && p.dp == d && p.split == s; };
+    P p;
+    CHECK(plan(6794, 37888, 3584, 256, &p) == V3D_OK && is(p, 2, 27 * 148, -1, 1));
+    CHECK(plan(6794, 4608, 3584, 256, &p) == V3D_OK && is(p, 2, 27 * 18, -1, 1));
+    CHECK(plan(6794, 3584, 3584, 256, &p) == V3D_OK && p.kernel == 3);
+    CHECK(plan(6794, 3584, 18944, 256, &p) == V3D_OK && is(p, 2, 378, 1, 2));
+    CHECK(plan(960, 3584, 18944, 256, &p) == V3D_OK && is(p, 2, 56, 0, 4));
+    CHECK(plan(960, 4608, 3584, 256, &p) == V3D_OK && p.kernel == 1);
+    CHECK(plan(4, 3584, 3584, 256, &p) == V3D_OK && p.kernel == 0);          // skinny (decode) path
+    CHECK(plan(23328, 1152, 1152, 256, &p) == V3D_OK && p.kernel == 1);      // N % 256 != 0: only the 128 x 128 tile fits
+    CHECK(plan(16, 100, 64, 256, &p) == V3D_E_INVALID && std::strstr(v3d_last_error(), "bad shape") != nullptr);
+    CHECK(plan(16, 128, 64, 0, &p) == V3D_E_INVALID);
+    CHECK(v3d_gemm_plan_host(16, 128, 64, 256, nullptr, &p.tiles, &p.dp, &p.split) == V3D_E_INVALID && std::strstr(v3d_last_error(), "null pointer") != nullptr);
+    const int chips[6] = {8, 16, 64, 104, 256, 304};
+    int seen = 0;
+    for (int it = 0; it < 4000; ++it) {
+      const int M = 9 + std::rand() % 29991, N = 256 * (1 + std::rand() % 159), K = 64 * (1 + std::rand() % 319), slots = chips[std::rand() % 6];
+      CHECK(plan(M, N, K, slots, &p) == V3D_OK && p.kernel >= 1 && p.kernel <= 3);
+      if (p.dp < 0) { CHECK(p.split == 1); continue; }
+      ++seen;
+      const int grid = slots & ~7, nt = K / 64, T = p.tiles - p.dp * grid, split = p.split, wx = grid / 8, gpt = nt / 2;
+      CHECK(p.kernel == 2 && p.tiles == ((M + 255) / 256) * (N / 256));
+      CHECK(split >= 2 && split <= 4 && T > 0 && T * split <= grid);         // no chunk without a workgroup
+      CHECK(nt % 2 == 0 && gpt >= 2 * split);                                // no chunk shorter than two granules
+      std::vector<int> owner((size_t)split * T, -1);                         // [chunk][tile] -> workgroup
+      for (int b = 0; b < grid; ++b) {
+        const int g = (b & 7) * wx + (b >> 3);
+        if (g < split * T) { CHECK(owner[(size_t)g] == -1); owner[(size_t)g] = b; }
+      }
+      for (int j = 0; j < T; ++j) {
+        const int b0 = owner[(size_t)j];
+        CHECK(b0 >= 0);
+        const int g0 = (b0 & 7) * wx + (b0 >> 3);
+        for (int c = 1; c < split; ++c) {
+          const int fg = c * T + g0, partner = (fg % wx) * 8 + fg / wx;      // the kernel's partner formula
+          CHECK(partner < grid && partner == owner[(size_t)c * T + j]);
+        }
+      }
+      for (int c = 0; c < split; ++c) CHECK(2 * ((c + 1) * gpt / split) - 2 * (c * gpt / split) >= 2);
+      CHECK(2 * (split * gpt / split) == nt);
+    }
+    CHECK(seen > 50);
+  }
   std::puts("host_selftest ok");
   return 0;
 }

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <string.h>
 
 #include "v3d.h"
 
@@ -19,6 +20,20 @@ inline int check_launch(const char* what) {
     return V3D_E_LAUNCH;
   }
   return V3D_OK;
+}
+
+// One launch of a kernel whose dynamic LDS exceeds the default limit: the attribute is set once per instantiation.  `who` names
+// the entry point, with an optional " (kernel form)" behind it that only the launch error carries.
+template <auto KERNEL, int LDS, int BLOCK, typename Args>
+inline int launch_big_lds(const Args& p, int grid, const char* who, hipStream_t st) {
+  static bool attr_done = false;
+  if (!attr_done) {
+    hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    if (e != hipSuccess) { set_error("%.*s: LDS attribute: %s", (int)strcspn(who, " "), who, hipGetErrorString(e)); return V3D_E_LAUNCH; }
+    attr_done = true;
+  }
+  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(BLOCK), LDS, st, p);
+  return check_launch(who);
 }
 
 #define V3D_REQUIRE(cond, ...)          \
