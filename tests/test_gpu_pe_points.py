@@ -199,3 +199,64 @@ def test_fused_points_refuses_bad_arguments(ops):
     with pytest.raises(V3DError, match="another dtype / width / number of points"):
         ops.visual_tokens(feat, torch.zeros((1, 14, 14, 9, 3), dtype=torch.int32, device="cuda"),
                           ops.Sin3DTable(256, 301, torch.float16, "cuda", n_points=5), n_points=9)
+
+
+# ------------------------------------------------------------------------------ the four PE sources of the shared token-row body
+
+
+def _clamped_ids(ops, kind, V):
+    """Patch-constant coordinates drawn past both ends of the voxel range, so that the ids include 0 and the last id of an axis."""
+    dt = PC.DT[kind]
+    gen = torch.Generator().manual_seed(77 + V)
+    cell = (torch.rand((V, 14, 14, 3), generator=gen) - 0.5) * torch.tensor([40.0, 40.0, 14.0])
+    coords = torch.zeros((V, 384, 384, 3))
+    coords[:, :378, :378] = cell.repeat_interleave(27, dim=1).repeat_interleave(27, dim=2)
+    _, vox, ids = ops.coord_pool_voxel(coords.to(dt).cuda())
+    assert ids.min().item() == 0 and ids[..., :2].max().item() == 300 and ids[..., 2].max().item() == 100
+    assert torch.equal(vox.float().to(torch.int32), ids)          # r = rint of a T value: the voxel coordinate IS the id
+    return vox, ids
+
+
+def _four_forms_agree(ops, kind, V, C, pool, newline_on):
+    dt, n = PC.DT[kind], 14
+    vox, ids = _clamped_ids(ops, kind, V)
+    gen = torch.Generator().manual_seed(C + 2 * pool + newline_on)
+    feat = torch.randn((V, 729 if pool else n * n, C), generator=gen).to(dt).cuda()
+    newline = torch.randn(C, generator=gen).to(dt).cuda() if newline_on else None
+    rows, vec = V * n * (n + 1 if newline_on else n), 4 if kind == "f32" else 8
+    forms = {
+        "axis table": lambda out: ops.visual_tokens(feat, ids, ops.Sin3DTable(C, 301, dt, "cuda"), newline, pool=pool, out=out),
+        "points table": lambda out: ops.visual_tokens_points(feat, ids=ids[..., None, :], table=ops.Sin3DTable(C, 301, dt, "cuda", points_layout=True),
+                                                             newline=newline, pool=pool, out=out),
+        "trig on the fly": lambda out: ops.visual_tokens_points(feat, pts=vox[..., None, :], newline=newline, pool=pool, out=out),
+    }
+    if kind != "f32":       # v3d_visual_tokens_rows is the 16-bit training form: it refuses f32 (tests/test_gpu_pe_mlp.py)
+        forms["PE rows"] = lambda out: ops.visual_tokens_rows(feat, ops.sin3d_pe(vox, C).reshape(-1, C), newline, pool=pool, out=out)
+    outs = {}
+    for name, run in forms.items():
+        buf = torch.zeros((3 + rows + 2, C + vec), dtype=dt, device="cuda")[:, :C]       # `out` is a row slice of a wider buffer
+        run(buf[3:3 + rows])
+        assert not buf[:3].any() and not buf[3 + rows:].any(), name
+        outs[name] = buf[3:3 + rows]
+    first = outs["axis table"]
+    assert not torch.equal(first, ops.visual_tokens(feat, newline=newline, pool=pool))     # the PE took part
+    for name, out in outs.items():
+        bad = (out.view(torch.int32 if kind == "f32" else torch.int16) != first.view(torch.int32 if kind == "f32" else torch.int16)).nonzero()
+        assert bad.numel() == 0, f"{name} differs from the axis table at (row, channel) {bad[0].tolist()}: {out[tuple(bad[0])].item()} vs {first[tuple(bad[0])].item()}"
+
+
+@pytest.mark.parametrize("newline_on", [True, False])
+@pytest.mark.parametrize("pool", [True, False])
+@pytest.mark.parametrize("kind", ["f16", "bf16", "f32"])
+def test_one_point_pe_sources_agree(ops, kind, pool, newline_on):
+    """With P = 1 the PE sources of the shared token-row body compute the same value - T(pe_value(float(id), dim_t[j], j)) added to the
+    pooled value in T - so their outputs are equal bit for bit.  V = 2; 16-bit C = 104 (nf = 34: segments start at vector offsets 0, 2, 4,
+    vectors straddle two segments, channels 102-103 get no PE, 13 vectors < 64 lanes), f32 C = 52 (nf = 17)."""
+    _four_forms_agree(ops, kind, 2, 52 if kind == "f32" else 104, pool, newline_on)
+
+
+@pytest.mark.parametrize("kind,C", [("f32", 2060), ("bf16", 4120)])
+def test_one_point_pe_sources_agree_past_512_lanes(ops, kind, C):
+    """515 vectors per token > 512 lanes: the lane-strided loop runs twice (f32 C = 2060, nf = 686, offset 2; bf16 C = 4120 so that the
+    PE-rows form, which has no f32, takes the second trip as well)."""
+    _four_forms_agree(ops, kind, 1, C, True, True)

@@ -3,7 +3,7 @@
 //
 // Compiled with -ffp-contract=off: every f32 operation below is a single IEEE operation in the
 // order written, so results are reproducible against the CPU oracle.
-#include "v3d_common.h"
+#include "visual_common.h"
 
 namespace v3d {
 
@@ -206,25 +206,7 @@ __global__ __launch_bounds__(256) void bounds_fold_kernel(const float* __restric
   }
 }
 
-// ----------------------------------------------------------------------------------------
-// K4  discrete_coords (llava/model/llava_arch.py:259-272), torch-on-CPU dtype rules
-// (pinned exhaustively for fp16 by tests/golden/discrete_coords.npz):
-//   clamp; t = T(x - lo); q = T(float(t) / float(voxel)); r = rint(q)
-// ----------------------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ float voxelise(float x, float lo, float hi, float voxel) {
-  // torch.maximum / minimum propagate NaN
-  if (x == x) {
-    x = x < lo ? lo : x;
-    x = x > hi ? hi : x;
-  }
-  const float t = round_to<T>(__fsub_rn(x, lo));
-  const float q = round_to<T>(__fdiv_rn(t, voxel));
-  return rintf(q);
-}
-
-struct Range { float lo[3], hi[3], voxel; };
-
+// K4  discrete_coords: voxelise (visual_common.h) on arbitrary [..., 3] points
 template <typename T>
 __global__ __launch_bounds__(256) void discrete_coords_kernel(const T* __restrict__ xyz, int64_t n3, Range rg,
                                                               T* __restrict__ vox, int32_t* __restrict__ ids) {
@@ -448,14 +430,6 @@ extern "C" int v3d_unproject_bounds_u16(const uint16_t* depth, const float* intr
   if (int e = check_launch("v3d_unproject_bounds_u16")) return e;
   hipLaunchKernelGGL(bounds_fold_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, V * BOUNDS_BLOCKS, bounds);
   return check_launch("v3d_unproject_bounds_u16");
-}
-
-static int fill_range(Range& rg, const float* lo, const float* hi, float voxel, const char* who) {
-  V3D_REQUIRE(lo && hi, "%s: min/max range pointers are null", who);
-  V3D_REQUIRE(voxel > 0.0f, "%s: voxel_size must be > 0", who);
-  for (int i = 0; i < 3; ++i) { rg.lo[i] = lo[i]; rg.hi[i] = hi[i]; }
-  rg.voxel = voxel;
-  return V3D_OK;
 }
 
 extern "C" int v3d_discrete_coords(const void* xyz, int dtype, int64_t N, const float* min_xyz_host,

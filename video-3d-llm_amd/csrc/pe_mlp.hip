@@ -8,10 +8,9 @@
 //
 // The rounding points are the 16-bit torch modules' own ("The MLP position encoding, stated once"):
 //     z = T(x w0^T + b0),  h = relu(T(LN(z) g + beta)) with f32 row statistics,  pe = T(h w3^T + b3),  token = T(pooled + pe).
-// v3d_visual_tokens and v3d_visual_tokens_points are not touched so that their code objects stay what they are: bilinear_tap is
-// restated here.  Compiled with -ffp-contract=off (the bilinear blend rounds like the reference's f32 ops); the multiply-adds that
+// Compiled with -ffp-contract=off (the bilinear blend rounds like the reference's f32 ops: visual_common.h); the multiply-adds that
 // are meant to be fused are written as fmaf.
-#include "v3d_common.h"
+#include "visual_common.h"
 
 namespace v3d {
 
@@ -71,82 +70,31 @@ __global__ __launch_bounds__(256) void pe_mlp_hidden_kernel(const T* __restrict_
 }
 
 // ----------------------------------------------------------------------------------------
-// v3d_visual_tokens with PE rows.  One workgroup = one OUTPUT token row of C channels, lane = one 16-byte vector of channels, as in
-// visual_tokens.hip; the PE operand is row (v, oh, ow) of pe [V n n, C] (row stride pe_stride) instead of three table rows.
-//   POOL   : x = h0*(w0*x00 + w1*x01) + h1*(w0*x10 + w1*x11) in f32, rounded to T
+// v3d_visual_tokens with PE rows: token_row_body (visual_common.h) with the PE operand read from row (v, oh, ow) of
+// pe [V n n, C] (row stride pe_stride) instead of three table rows,
 //   PE     : x = T(x + pe[row][channel])
-//   NEWLINE: row (v, oh, n) of the output is `newline`
 // ----------------------------------------------------------------------------------------
-struct RowTaps { int i0, i1; float l0, l1; };
+template <typename T>
+struct RowPE {
+  static constexpr bool ON = true;
+  const T* pe;
+  int64_t pe_stride;
+  const uint4* prow;
+  uint4 p;
 
-__device__ __forceinline__ RowTaps rows_bilinear_tap(int o, int n_in, int n_out) {
-  const float scale = __fdiv_rn((float)n_in, (float)n_out);
-  float src = fmaf(scale, (float)o + 0.5f, -0.5f);   // single rounding, as ATen's builds do
-  src = src < 0.0f ? 0.0f : src;
-  RowTaps t;
-  t.i0 = (int)src;
-  t.i1 = t.i0 + (t.i0 < n_in - 1 ? 1 : 0);
-  t.l1 = __fsub_rn(src, (float)t.i0);
-  t.l0 = __fsub_rn(1.0f, t.l1);
-  return t;
-}
+  __device__ __forceinline__ void token(size_t cell) { prow = reinterpret_cast<const uint4*>(pe + cell * pe_stride); }
+  __device__ __forceinline__ void vector(int k) { p = prow[k]; }      // the PE row's load is issued first, ahead of the feature rows
+  __device__ __forceinline__ void operand(int) {}
+  __device__ __forceinline__ float value(int j) const { return vec_get<T>(p, j); }
+};
 
 template <typename T, bool POOL>
 __global__ __launch_bounds__(512) void visual_tokens_rows_kernel(const T* __restrict__ feat, const T* __restrict__ pe, int64_t pe_stride,
                                                                  const T* __restrict__ newline, T* __restrict__ out, int64_t out_stride,
                                                                  int side, int n, int C, int newline_on) {
-  constexpr int VEC = 16 / sizeof(T);
-  const int vpt = C / VEC;
-  const int cols = newline_on ? n + 1 : n;
-  const int tok = blockIdx.x;
-  const int v = tok / (n * cols);
-  const int rem = tok - v * (n * cols);
-  const int oh = rem / cols, ow = rem - oh * cols;
-  uint4* dst = reinterpret_cast<uint4*>(out + (size_t)tok * out_stride);
-
-  if (ow == n) {  // newline row
-    const uint4* nl = reinterpret_cast<const uint4*>(newline);
-    for (int k = threadIdx.x; k < vpt; k += blockDim.x) dst[k] = nl[k];
-    return;
-  }
-
-  const int in_side = POOL ? side : n;
-  const T* frame = feat + (size_t)v * in_side * in_side * C;
-  RowTaps th, tw;
-  const uint4 *r00, *r01, *r10, *r11;
-  if (POOL) {
-    th = rows_bilinear_tap(oh, side, n);
-    tw = rows_bilinear_tap(ow, side, n);
-    r00 = reinterpret_cast<const uint4*>(frame + ((size_t)th.i0 * side + tw.i0) * C);
-    r01 = reinterpret_cast<const uint4*>(frame + ((size_t)th.i0 * side + tw.i1) * C);
-    r10 = reinterpret_cast<const uint4*>(frame + ((size_t)th.i1 * side + tw.i0) * C);
-    r11 = reinterpret_cast<const uint4*>(frame + ((size_t)th.i1 * side + tw.i1) * C);
-  } else {
-    r00 = reinterpret_cast<const uint4*>(frame + ((size_t)oh * n + ow) * C);
-    r01 = r10 = r11 = r00;
-  }
-  const uint4* prow = reinterpret_cast<const uint4*>(pe + ((size_t)(v * n + oh) * n + ow) * pe_stride);
-
-  for (int k = threadIdx.x; k < vpt; k += blockDim.x) {
-    float x[VEC];
-    const uint4 p = prow[k];
-    if (POOL) {
-      const uint4 a = r00[k], b = r01[k], c = r10[k], d = r11[k];
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        const float top = __fadd_rn(__fmul_rn(tw.l0, vec_get<T>(a, j)), __fmul_rn(tw.l1, vec_get<T>(b, j)));
-        const float bot = __fadd_rn(__fmul_rn(tw.l0, vec_get<T>(c, j)), __fmul_rn(tw.l1, vec_get<T>(d, j)));
-        x[j] = round_to<T>(__fadd_rn(__fmul_rn(th.l0, top), __fmul_rn(th.l1, bot)));
-      }
-    } else {
-      const uint4 a = r00[k];
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) x[j] = vec_get<T>(a, j);
-    }
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) x[j] = __fadd_rn(x[j], vec_get<T>(p, j));
-    dst[k] = vec_pack<T>(x);
-  }
+  RowPE<T> src;
+  src.pe = pe; src.pe_stride = pe_stride;
+  token_row_body<T, POOL>(feat, newline, out, out_stride, side, n, C, newline_on, src);
 }
 
 // dpe[(v, oh, ow), :] = dout[(v, oh, ow) among cols = n + 1 | n rows per grid row, :]: the PE add passes the gradient through, the
@@ -241,25 +189,16 @@ extern "C" int v3d_pe_mlp_hidden(const void* x, const void* w0, const void* b0, 
 extern "C" int v3d_visual_tokens_rows(const void* feat, const void* pe, int64_t pe_stride, const void* newline, void* out, int64_t out_stride,
                                       int dtype, int V, int side, int n, int C, int flags, void* stream) {
   const bool pool = flags & V3D_VT_POOL, nl = flags & V3D_VT_NEWLINE;
-  V3D_REQUIRE(feat && pe && out, "v3d_visual_tokens_rows: null pointer");
+  V3D_REQUIRE(pe, "v3d_visual_tokens_rows: null pointer");
   V3D_REQUIRE(!(flags & ~(V3D_VT_POOL | V3D_VT_PE | V3D_VT_NEWLINE)), "v3d_visual_tokens_rows: flags %d (POOL, PE, NEWLINE)", flags);
-  V3D_REQUIRE(!nl || newline, "v3d_visual_tokens_rows: NEWLINE needs a newline row");
-  V3D_REQUIRE(V > 0 && n > 0 && C > 0 && (!pool || side >= n), "v3d_visual_tokens_rows: bad shape V=%d side=%d n=%d C=%d", V, side, n, C);
-  V3D_REQUIRE(C % 8 == 0, "v3d_visual_tokens_rows: C=%d must be a multiple of 8", C);
-  V3D_REQUIRE(out_stride >= C && out_stride % 8 == 0, "v3d_visual_tokens_rows: out_stride=%lld", (long long)out_stride);
+  TokenRowPlan plan;
+  if (int e = plan_token_rows("v3d_visual_tokens_rows", feat, pe, newline, out, out_stride, 8, V, side, n, C, flags, &plan)) return e;
   V3D_REQUIRE(pe_stride >= C && pe_stride % 8 == 0, "v3d_visual_tokens_rows: pe_stride=%lld", (long long)pe_stride);
-  V3D_REQUIRE(aligned16(feat) && aligned16(out) && aligned16(pe) && (!nl || aligned16(newline)),
-              "v3d_visual_tokens_rows: pointers must be 16-byte aligned");
-  const int64_t tokens = (int64_t)V * n * (nl ? n + 1 : n);
-  V3D_REQUIRE(tokens < (1ll << 31), "v3d_visual_tokens_rows: too many tokens");
-  const int vpt = C / 8;
-  int threads = ((vpt + 63) / 64) * 64;
-  if (threads > 512) threads = 512;
   hipStream_t st = (hipStream_t)stream;
   V3D_PE_MLP_16(dtype, {
-    if (pool) hipLaunchKernelGGL((visual_tokens_rows_kernel<T, true>), dim3((unsigned)tokens), dim3(threads), 0, st, (const T*)feat, (const T*)pe,
+    if (pool) hipLaunchKernelGGL((visual_tokens_rows_kernel<T, true>), dim3((unsigned)plan.tokens), dim3(plan.threads), 0, st, (const T*)feat, (const T*)pe,
                                  pe_stride, (const T*)newline, (T*)out, out_stride, side, n, C, nl ? 1 : 0);
-    else hipLaunchKernelGGL((visual_tokens_rows_kernel<T, false>), dim3((unsigned)tokens), dim3(threads), 0, st, (const T*)feat, (const T*)pe,
+    else hipLaunchKernelGGL((visual_tokens_rows_kernel<T, false>), dim3((unsigned)plan.tokens), dim3(plan.threads), 0, st, (const T*)feat, (const T*)pe,
                             pe_stride, (const T*)newline, (T*)out, out_stride, side, n, C, nl ? 1 : 0);
   });
   return check_launch("v3d_visual_tokens_rows");

@@ -5,32 +5,11 @@
 //   v3d_sin3d_pe_points          : the same module for arbitrary coordinates, xyz [N,P,3] -> [N,E]
 //   v3d_visual_tokens_points     : bilinear pool + PE(P points; table or on-the-fly trig) add + newline rows
 //
-// The shipped "avg-discrete-sin3d" path keeps its own kernels (geometry.hip, visual_tokens.hip), and those files are
-// not touched so that their code objects stay what they are: voxelise, pe_value and bilinear_tap are restated here
-// word for word.  Compiled with -ffp-contract=off like visual_tokens.hip.
-#include "v3d_common.h"
+// The one-point "avg-discrete-sin3d" path has its own aggregation and fused kernel (geometry.hip, visual_tokens.hip); the voxeliser,
+// pe_value and the token-row body are shared with them (visual_common.h).  Compiled with -ffp-contract=off like visual_tokens.hip.
+#include "visual_common.h"
 
 namespace v3d {
-
-// geometry.hip `voxelise`: clamp; t = T(x - lo); q = T(float(t) / float(voxel)); r = rint(q)
-template <typename T>
-__device__ __forceinline__ float pts_voxelise(float x, float lo, float hi, float voxel) {
-  if (x == x) {
-    x = x < lo ? lo : x;
-    x = x > hi ? hi : x;
-  }
-  const float t = round_to<T>(__fsub_rn(x, lo));
-  const float q = round_to<T>(__fdiv_rn(t, voxel));
-  return rintf(q);
-}
-
-struct PtsRange { float lo[3], hi[3], voxel; };
-
-// visual_tokens.hip `pe_value`: IEEE f32 division, trig in double rounded once to f32
-__device__ __forceinline__ float pts_pe_value(float p, float dim_t, int j) {
-  const float arg = __fdiv_rn(p, dim_t);
-  return (float)((j & 1) ? cos((double)arg) : sin((double)arg));
-}
 
 constexpr int kSide = 384, kPatch = 27, kCells = 14;     // llava_arch.py:245 hard-codes 14 x 27
 
@@ -39,10 +18,10 @@ __host__ __device__ inline int points_of_mode(int mode) {
 }
 
 template <typename T>
-__device__ __forceinline__ void store_point(float x, int ch, size_t o, const PtsRange& rg, T* pts, T* vox, int32_t* ids) {
+__device__ __forceinline__ void store_point(float x, int ch, size_t o, const Range& rg, T* pts, T* vox, int32_t* ids) {
   if (pts) pts[o] = from_f32<T>(x);
   if (vox || ids) {
-    const float r = pts_voxelise<T>(x, round_to<T>(rg.lo[ch]), round_to<T>(rg.hi[ch]), rg.voxel);
+    const float r = voxelise<T>(x, round_to<T>(rg.lo[ch]), round_to<T>(rg.hi[ch]), rg.voxel);
     if (vox) vox[o] = from_f32<T>(r);
     if (ids) ids[o] = (int32_t)r;
   }
@@ -55,7 +34,7 @@ __device__ __forceinline__ void store_point(float x, int ch, size_t o, const Pts
 // ----------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void coord_sample_kernel(const T* __restrict__ coords, int64_t total, int P, int mode,
-                                                           PtsRange rg, T* __restrict__ pts, T* __restrict__ vox,
+                                                           Range rg, T* __restrict__ pts, T* __restrict__ vox,
                                                            int32_t* __restrict__ ids) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int ch = (int)(i % 3);
@@ -81,7 +60,7 @@ __global__ __launch_bounds__(256) void coord_sample_kernel(const T* __restrict__
 // in LDS, and lanes 0..41 fold the 27 columns of their (patch, channel).
 // ----------------------------------------------------------------------------------------
 template <typename T>
-__global__ __launch_bounds__(320) void coord_minmax_kernel(const T* __restrict__ coords, PtsRange rg, T* __restrict__ pts,
+__global__ __launch_bounds__(320) void coord_minmax_kernel(const T* __restrict__ coords, Range rg, T* __restrict__ pts,
                                                            T* __restrict__ vox, int32_t* __restrict__ ids) {
   constexpr int VEC = 16 / sizeof(T);
   constexpr int ROW = kSide * 3;             // 1152 elements; the 6 dropped columns ride along and are never folded
@@ -147,7 +126,7 @@ struct PointsLayout {
 };
 
 __host__ inline PointsLayout points_layout(int nf, int P, int vec) {
-  PointsLayout l = {0, ((nf + vec - 1) / vec) * vec + vec, 0u, 0u};
+  PointsLayout l = {0, table_row_elems(nf, vec), 0u, 0u};
   bool seen[8] = {false, false, false, false, false, false, false, false};
   for (int q = 0; q < 3 * P; ++q) {
     const int s = (int)(((int64_t)q * nf) % vec);
@@ -166,7 +145,7 @@ __global__ __launch_bounds__(256) void sin3d_table_points_kernel(const float* __
   const int64_t total = (int64_t)n_ids * nf;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int id = (int)(i / nf), j = (int)(i - (int64_t)id * nf);
-    const T t = from_f32<T>(pts_pe_value((float)id, dim_t[j], j));
+    const T t = from_f32<T>(pe_value((float)id, dim_t[j], j));
     for (int c = 0; c < lay.n_copies; ++c) {
       const int shift = (int)((lay.shift_of_copy >> (4 * c)) & 15u);
       table[((size_t)c * n_ids + id) * lay.row_elems + shift + j] = t;
@@ -187,16 +166,14 @@ __global__ __launch_bounds__(256) void sin3d_pe_points_kernel(const T* __restric
     float val = 0.0f;
     if (q < segs) {
       const int j = c - q * nf;
-      val = pts_pe_value(to_f32(xyz[tok * segs + q]), dim_t[j], j);
+      val = pe_value(to_f32(xyz[tok * segs + q]), dim_t[j], j);
     }
     out[i] = from_f32<T>(val);
   }
 }
 
 // ----------------------------------------------------------------------------------------
-// The fused visual-token kernel with P points.  Same shape as visual_tokens_kernel: one workgroup = one OUTPUT
-// token row, lane = one 16-byte vector of channels, taps and blend weights in SGPRs, same rounding points (pooled
-// value rounded to T, then the add rounded to T).  What differs is the PE operand of a lane:
+// The fused visual-token kernel with P points: token_row_body (visual_common.h) with this PE operand of a lane:
 //
 //   table : segments q0, q1 of the lane's first and last channel, id = ids[token][q] (4-byte loads from the token's
 //           12*P bytes, which every lane of the workgroup shares), one aligned 16-byte load from id0's row of the
@@ -204,20 +181,6 @@ __global__ __launch_bounds__(256) void sin3d_pe_points_kernel(const T* __restric
 //   CONT  : x = pts[token][q] per channel, T(pe_value(x, dim_t[j], j)) on the fly (the reference's rule for a
 //           type without `discrete`; also `avg-sin3d` with P = 1)
 // ----------------------------------------------------------------------------------------
-struct PtsTaps { int i0, i1; float l0, l1; };
-
-__device__ __forceinline__ PtsTaps pts_bilinear_tap(int o, int n_in, int n_out) {
-  const float scale = __fdiv_rn((float)n_in, (float)n_out);
-  float src = fmaf(scale, (float)o + 0.5f, -0.5f);
-  src = src < 0.0f ? 0.0f : src;
-  PtsTaps t;
-  t.i0 = (int)src;
-  t.i1 = t.i0 + (t.i0 < n_in - 1 ? 1 : 0);
-  t.l1 = __fsub_rn(src, (float)t.i0);
-  t.l0 = __fsub_rn(1.0f, t.l1);
-  return t;
-}
-
 template <typename T>
 struct PointsArgs {
   const T* feat;
@@ -243,85 +206,41 @@ __device__ __forceinline__ uint4 points_table_vec(const PointsArgs<T>& a, int id
   return row[k - start / VEC];
 }
 
-template <typename T, bool POOL, bool CONT>
-__global__ __launch_bounds__(512) void visual_tokens_points_kernel(PointsArgs<T> a) {
-  constexpr int VEC = 16 / sizeof(T);
-  const int n = a.n, C = a.C, side = a.side, nf = a.nf;
-  const int vpt = C / VEC;
-  const int cols = a.newline_on ? n + 1 : n;
-  const int tok = blockIdx.x;
-  const int v = tok / (n * cols);
-  const int rem = tok - v * (n * cols);
-  const int oh = rem / cols, ow = rem - oh * cols;
-  uint4* dst = reinterpret_cast<uint4*>(a.out + (size_t)tok * a.out_stride);
+template <typename T, bool CONT>
+struct PointsPE {
+  static constexpr bool ON = true;
+  static constexpr int VEC = 16 / sizeof(T);
+  const PointsArgs<T>& a;
+  size_t tbase;             // this token's ids / points
+  int id0, id1;
+  uint4 p;                  // table source: the lane's table vector(s), OR-ed
+  int c0, q0, edge;         // CONT source: first channel and segment of the lane's vector, channels of it that belong to q0,
+  float xa, xb;             //              and the coordinates of segments q0 and q0 + 1
 
-  if (ow == n) {  // newline row
-    const uint4* nl = reinterpret_cast<const uint4*>(a.newline);
-    for (int k = threadIdx.x; k < vpt; k += blockDim.x) dst[k] = nl[k];
-    return;
-  }
-
-  const int in_side = POOL ? side : n;
-  const T* frame = a.feat + (size_t)v * in_side * in_side * C;
-  PtsTaps th, tw;
-  const uint4 *r00, *r01, *r10, *r11;
-  if (POOL) {
-    th = pts_bilinear_tap(oh, side, n);
-    tw = pts_bilinear_tap(ow, side, n);
-    r00 = reinterpret_cast<const uint4*>(frame + ((size_t)th.i0 * side + tw.i0) * C);
-    r01 = reinterpret_cast<const uint4*>(frame + ((size_t)th.i0 * side + tw.i1) * C);
-    r10 = reinterpret_cast<const uint4*>(frame + ((size_t)th.i1 * side + tw.i0) * C);
-    r11 = reinterpret_cast<const uint4*>(frame + ((size_t)th.i1 * side + tw.i1) * C);
-  } else {
-    r00 = reinterpret_cast<const uint4*>(frame + ((size_t)oh * n + ow) * C);
-    r01 = r10 = r11 = r00;
-  }
-
-  const int segs = 3 * a.P;
-  const size_t tbase = ((size_t)(v * n + oh) * n + ow) * segs;     // this token's ids / points
-
-  for (int k = threadIdx.x; k < vpt; k += blockDim.x) {
-    const int c0 = k * VEC;
-    const int q0 = c0 / nf, q1 = (c0 + VEC - 1) / nf;
+  __device__ __forceinline__ void token(size_t cell) { tbase = cell * (3 * a.P); }
+  __device__ __forceinline__ void vector(int k) {
+    const int segs = 3 * a.P, c0 = k * VEC;
+    const int q0 = c0 / a.nf, q1 = (c0 + VEC - 1) / a.nf;
     // The lane's ids are asked for BEFORE the feature rows: vector loads return in order, so a table load that waits for its id
     // would otherwise wait for the four feature loads as well, and the kernel's longest chain would grow by one memory round trip.
-    int id0 = 0, id1 = 0;
+    id0 = id1 = 0;
     if (!CONT) {
       id0 = a.ids[tbase + (q0 < segs ? q0 : segs - 1)];
       id1 = a.ids[tbase + (q1 < segs ? q1 : segs - 1)];
     }
-    float x[VEC];
-    if (POOL) {
-      const uint4 p00 = r00[k], p01 = r01[k], p10 = r10[k], p11 = r11[k];
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        const float top = __fadd_rn(__fmul_rn(tw.l0, vec_get<T>(p00, j)), __fmul_rn(tw.l1, vec_get<T>(p01, j)));
-        const float bot = __fadd_rn(__fmul_rn(tw.l0, vec_get<T>(p10, j)), __fmul_rn(tw.l1, vec_get<T>(p11, j)));
-        x[j] = round_to<T>(__fadd_rn(__fmul_rn(th.l0, top), __fmul_rn(th.l1, bot)));
-      }
-    } else {
-      const uint4 p00 = r00[k];
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) x[j] = vec_get<T>(p00, j);
-    }
-
+  }
+  __device__ __forceinline__ void operand(int k) {
+    const int segs = 3 * a.P, nf = a.nf;
+    c0 = k * VEC;
+    q0 = c0 / nf;
     if (CONT) {
       // the vector overlaps segments q0 and (at most) q0 + 1, nf being >= VEC
-      const int edge = (q0 + 1) * nf - c0;                        // channels of this vector that belong to q0
-      const float xa = q0 < segs ? to_f32(a.pts[tbase + q0]) : 0.0f;
-      const float xb = (q0 + 1 < segs && edge < VEC) ? to_f32(a.pts[tbase + q0 + 1]) : 0.0f;
-      const int j0 = c0 - q0 * nf;
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        const bool first = j < edge;
-        const int q = first ? q0 : q0 + 1;
-        const int f = first ? j0 + j : j - edge;
-        float pe = 0.0f;
-        if (q < segs) pe = round_to<T>(pts_pe_value(first ? xa : xb, a.dim_t[f], f));
-        x[j] = __fadd_rn(x[j], pe);
-      }
+      edge = (q0 + 1) * nf - c0;                                  // channels of this vector that belong to q0
+      xa = q0 < segs ? to_f32(a.pts[tbase + q0]) : 0.0f;
+      xb = (q0 + 1 < segs && edge < VEC) ? to_f32(a.pts[tbase + q0 + 1]) : 0.0f;
     } else {
-      uint4 p = make_uint4(0, 0, 0, 0);
+      const int q1 = (c0 + VEC - 1) / nf;
+      p = make_uint4(0, 0, 0, 0);
       if (q0 < segs) {
         p = points_table_vec(a, id0, q0, k);
         if (q1 != q0 && q1 < segs) {
@@ -329,24 +248,26 @@ __global__ __launch_bounds__(512) void visual_tokens_points_kernel(PointsArgs<T>
           p.x |= q.x; p.y |= q.y; p.z |= q.z; p.w |= q.w;        // disjoint support: padding is zero bits
         }
       }
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) x[j] = __fadd_rn(x[j], vec_get<T>(p, j));
     }
-    dst[k] = vec_pack<T>(x);
   }
+  __device__ __forceinline__ float value(int j) const {
+    if (!CONT) return vec_get<T>(p, j);
+    const bool first = j < edge;
+    const int q = first ? q0 : q0 + 1;
+    const int f = first ? c0 - q0 * a.nf + j : j - edge;
+    return q < 3 * a.P ? round_to<T>(pe_value(first ? xa : xb, a.dim_t[f], f)) : 0.0f;
+  }
+};
+
+template <typename T, bool POOL, bool CONT>
+__global__ __launch_bounds__(512) void visual_tokens_points_kernel(PointsArgs<T> a) {
+  PointsPE<T, CONT> src{a};
+  token_row_body<T, POOL>(a.feat, a.newline, a.out, a.out_stride, a.side, a.n, a.C, a.newline_on, src);
 }
 
 }  // namespace v3d
 
 using namespace v3d;
-
-static int fill_pts_range(PtsRange& rg, const float* lo, const float* hi, float voxel, const char* who) {
-  V3D_REQUIRE(lo && hi, "%s: min/max range pointers are null", who);
-  V3D_REQUIRE(voxel > 0.0f, "%s: voxel_size must be > 0", who);
-  for (int i = 0; i < 3; ++i) { rg.lo[i] = lo[i]; rg.hi[i] = hi[i]; }
-  rg.voxel = voxel;
-  return V3D_OK;
-}
 
 extern "C" int v3d_coord_points_voxel(const void* coords, int dtype, int V, int S, int patch, int mode,
                                       const float* min_xyz_host, const float* max_xyz_host, float voxel_size, void* pts,
@@ -358,8 +279,8 @@ extern "C" int v3d_coord_points_voxel(const void* coords, int dtype, int V, int 
   V3D_REQUIRE(S == kSide && patch == kPatch,
               "v3d_coord_points_voxel: S=%d patch=%d: the sampled-point and min/max encodings are defined for S = 384, patch = 27 only "
               "(the reference hard-codes a 14 x 27 grid)", S, patch);
-  PtsRange rg;
-  if (int e = fill_pts_range(rg, min_xyz_host, max_xyz_host, voxel_size, "v3d_coord_points_voxel")) return e;
+  Range rg;
+  if (int e = fill_range(rg, min_xyz_host, max_xyz_host, voxel_size, "v3d_coord_points_voxel")) return e;
   hipStream_t st = (hipStream_t)stream;
   if (mode == V3D_PTS_MINMAX) {
     V3D_REQUIRE(aligned16(coords), "v3d_coord_points_voxel: coords must be 16-byte aligned");
@@ -418,41 +339,44 @@ extern "C" int v3d_sin3d_table_build_points(const float* dim_t, int embedding_si
   return check_launch("v3d_sin3d_table_build_points");
 }
 
+// both forms of PositionEmbeddingSine3D.forward on arbitrary coordinates: the one-point module is the P-point kernel with P = 1
+static int launch_sin3d_pe(const char* who, const void* xyz, int dtype, int64_t N, int P, const float* dim_t, int E, void* out, void* stream) {
+  int64_t blocks = (N * E + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  V3D_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(sin3d_pe_points_kernel<T>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream,
+                                               (const T*)xyz, N, P, dim_t, E, E / (3 * P), (T*)out));
+  return check_launch(who);
+}
+
+extern "C" int v3d_sin3d_pe(const void* xyz, int dtype, int64_t N, const float* dim_t, int embedding_size, void* out,
+                            void* stream) {
+  V3D_REQUIRE(xyz && dim_t && out, "v3d_sin3d_pe: null pointer");
+  V3D_REQUIRE(N >= 0 && embedding_size >= 3, "v3d_sin3d_pe: bad shape");
+  if (N == 0) return V3D_OK;
+  return launch_sin3d_pe("v3d_sin3d_pe", xyz, dtype, N, 1, dim_t, embedding_size, out, stream);
+}
+
 extern "C" int v3d_sin3d_pe_points(const void* xyz, int dtype, int64_t N, int n_points, const float* dim_t,
                                    int embedding_size, void* out, void* stream) {
   V3D_REQUIRE(xyz && dim_t && out, "v3d_sin3d_pe_points: null pointer");
   V3D_REQUIRE(N >= 0 && n_points >= 1 && embedding_size >= 3 * n_points, "v3d_sin3d_pe_points: bad shape N=%lld P=%d E=%d",
               (long long)N, n_points, embedding_size);
   if (N == 0) return V3D_OK;
-  int64_t blocks = (N * embedding_size + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  V3D_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(sin3d_pe_points_kernel<T>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream,
-                                               (const T*)xyz, N, n_points, dim_t, embedding_size,
-                                               embedding_size / (3 * n_points), (T*)out));
-  return check_launch("v3d_sin3d_pe_points");
+  return launch_sin3d_pe("v3d_sin3d_pe_points", xyz, dtype, N, n_points, dim_t, embedding_size, out, stream);
 }
 
 extern "C" int v3d_visual_tokens_points(const void* feat, const int32_t* ids, const void* pts, const void* table, int n_ids,
                                         const float* dim_t, int n_points, const void* newline, void* out, int64_t out_stride,
                                         int dtype, int V, int side, int n, int C, int flags, void* stream) {
   const bool pool = flags & V3D_VT_POOL, pe = flags & V3D_VT_PE, nl = flags & V3D_VT_NEWLINE, cont = flags & V3D_VT_CONTINUOUS;
-  V3D_REQUIRE(feat && out, "v3d_visual_tokens_points: null pointer");
   V3D_REQUIRE(pe, "v3d_visual_tokens_points: the PE flag is required (v3d_visual_tokens pools without one)");
   V3D_REQUIRE(cont ? (pts && dim_t) : (ids && table && n_ids > 0),
               "v3d_visual_tokens_points: PE needs pts and dim_t (CONTINUOUS) or ids and a table");
-  V3D_REQUIRE(!nl || newline, "v3d_visual_tokens_points: NEWLINE needs a newline row");
-  V3D_REQUIRE(V > 0 && n > 0 && C > 0 && (!pool || side >= n), "v3d_visual_tokens_points: bad shape V=%d side=%d n=%d C=%d", V, side, n, C);
   int nf, vec;
   if (int e = check_points_shape("v3d_visual_tokens_points", C, n_points, dtype, &nf, &vec)) return e;
-  V3D_REQUIRE(C % vec == 0, "v3d_visual_tokens_points: C=%d must be a multiple of %d", C, vec);
-  V3D_REQUIRE(out_stride >= C && out_stride % vec == 0, "v3d_visual_tokens_points: out_stride=%lld", (long long)out_stride);
-  V3D_REQUIRE(aligned16(feat) && aligned16(out) && (cont || aligned16(table)) && (!nl || aligned16(newline)),
-              "v3d_visual_tokens_points: pointers must be 16-byte aligned");
-  const int64_t tokens = (int64_t)V * n * (nl ? n + 1 : n);
-  V3D_REQUIRE(tokens < (1ll << 31), "v3d_visual_tokens_points: too many tokens");
-  const int vpt = C / vec;
-  int threads = ((vpt + 63) / 64) * 64;
-  if (threads > 512) threads = 512;
+  TokenRowPlan plan;
+  if (int e = plan_token_rows("v3d_visual_tokens_points", feat, cont ? nullptr : table, newline, out, out_stride, vec, V, side, n, C, flags, &plan))
+    return e;
   hipStream_t st = (hipStream_t)stream;
   V3D_DISPATCH_DTYPE(dtype, {
     PointsArgs<T> a;
@@ -460,10 +384,10 @@ extern "C" int v3d_visual_tokens_points(const void* feat, const int32_t* ids, co
     a.newline = (const T*)newline; a.out = (T*)out; a.out_stride = out_stride;
     a.lay = points_layout(nf, n_points, vec);
     a.n_ids = n_ids; a.P = n_points; a.nf = nf; a.side = side; a.n = n; a.C = C; a.newline_on = nl ? 1 : 0;
-    if (pool && cont) hipLaunchKernelGGL((visual_tokens_points_kernel<T, true, true>), dim3((unsigned)tokens), dim3(threads), 0, st, a);
-    else if (pool) hipLaunchKernelGGL((visual_tokens_points_kernel<T, true, false>), dim3((unsigned)tokens), dim3(threads), 0, st, a);
-    else if (cont) hipLaunchKernelGGL((visual_tokens_points_kernel<T, false, true>), dim3((unsigned)tokens), dim3(threads), 0, st, a);
-    else hipLaunchKernelGGL((visual_tokens_points_kernel<T, false, false>), dim3((unsigned)tokens), dim3(threads), 0, st, a);
+    if (pool && cont) hipLaunchKernelGGL((visual_tokens_points_kernel<T, true, true>), dim3((unsigned)plan.tokens), dim3(plan.threads), 0, st, a);
+    else if (pool) hipLaunchKernelGGL((visual_tokens_points_kernel<T, true, false>), dim3((unsigned)plan.tokens), dim3(plan.threads), 0, st, a);
+    else if (cont) hipLaunchKernelGGL((visual_tokens_points_kernel<T, false, true>), dim3((unsigned)plan.tokens), dim3(plan.threads), 0, st, a);
+    else hipLaunchKernelGGL((visual_tokens_points_kernel<T, false, false>), dim3((unsigned)plan.tokens), dim3(plan.threads), 0, st, a);
   });
   return check_launch("v3d_visual_tokens_points");
 }

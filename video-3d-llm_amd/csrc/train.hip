@@ -5,7 +5,7 @@
 //   v3d_visual_tokens_grad    gradient of get_2dPool (bilinear 27 -> 14) + "+ PE" (no parameters: passes through) + image_newline
 //                             insertion (llava_arch.py:191-210, 506-517, 307-328) with respect to the projector features and
 //                             to image_newline
-#include "v3d_common.h"
+#include "visual_common.h"
 
 namespace v3d {
 
@@ -96,19 +96,6 @@ __global__ __launch_bounds__(256) void cross_entropy_grad_kernel(const T* __rest
   }
 }
 
-struct Taps2 { int i0, i1; float l0, l1; };
-__device__ __forceinline__ Taps2 tap_of(int o, int n_in, int n_out) {       // the forward kernel's bilinear_tap
-  const float scale = __fdiv_rn((float)n_in, (float)n_out);
-  float src = fmaf(scale, (float)o + 0.5f, -0.5f);
-  src = src < 0.0f ? 0.0f : src;
-  Taps2 t;
-  t.i0 = (int)src;
-  t.i1 = t.i0 + (t.i0 < n_in - 1 ? 1 : 0);
-  t.l1 = __fsub_rn(src, (float)t.i0);
-  t.l0 = __fsub_rn(1.0f, t.l1);
-  return t;
-}
-
 // Gather form of upsample_bilinear2d_backward: one workgroup per INPUT token (frame v, row y, column x) sums, in f32 and in a
 // fixed order, weight_h * weight_w * dout[row of output (oh, ow)] over the <= 3 x 3 pooled outputs whose taps touch it.
 template <typename T>
@@ -122,7 +109,7 @@ __global__ __launch_bounds__(256) void visual_tokens_grad_kernel(const T* __rest
   float wh[4], ww[4];
   int nh = 0, nw = 0;
   for (int o = 0; o < n; ++o) {
-    const Taps2 t = tap_of(o, side, n);
+    const Taps t = bilinear_tap(o, side, n);       // the forward kernel's taps (visual_common.h)
     float wy = 0.f, wx = 0.f;
     if (t.i0 == y) wy += t.l0;
     if (t.i1 == y) wy += t.l1;

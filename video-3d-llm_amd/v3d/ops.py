@@ -251,17 +251,11 @@ def sin3d_pe(xyz, embedding_size, dim_t=None, temperature=10000, n_points=1):
 # ------------------------------------------------------------------------------ fusion
 
 
-def visual_tokens(feat, ids=None, table=None, newline=None, side=27, n=14, pool=True, out=None, n_points=1, pts=None, dim_t=None):
-    """K7 (+K5+K6) (+K8).  feat [V, side*side | n*n, C]; ids [V,n,n,3] int32; table Sin3DTable;
-    newline [C].  Returns / fills `out` [rows, C] (rows = V*n*(n+1) with newline else V*n*n);
-    `out` may be a row-slice view of a larger [S, C] buffer (the LLM's inputs_embeds).
-    n_points > 1 or pts given: the P-point encodings, through visual_tokens_points; the default call launches v3d_visual_tokens."""
-    if n_points > 1 or pts is not None:
-        return visual_tokens_points(feat, ids=ids, table=table, pts=pts, dim_t=dim_t, n_points=n_points, newline=newline, side=side,
-                                    n=n, pool=pool, out=out)
+def _token_rows(feat, newline, side, n, pool, out):
+    """What the three fused-kernel wrappers do first: feat on the device with the token count the pool flag implies, `out` allocated or
+    checked, newline in feat's dtype, the POOL / NEWLINE flag bits -> (feat, V, C, out, newline, flags)."""
     f = _dev(feat, "feat")
     V, T, C = f.shape
-    flags = (VT_POOL if pool else 0) | (VT_PE if table is not None else 0) | (VT_NEWLINE if newline is not None else 0)
     expect = side * side if pool else n * n
     if T != expect:
         raise V3DError(f"feat has {T} tokens per frame, expected {expect}")
@@ -270,9 +264,24 @@ def visual_tokens(feat, ids=None, table=None, newline=None, side=27, n=14, pool=
         out = torch.empty((rows, C), dtype=f.dtype, device=f.device)
     if out.dtype != f.dtype or out.shape[0] != rows or out.shape[1] != C or out.stride(1) != 1:
         raise V3DError(f"out must be [{rows},{C}] {f.dtype} with unit column stride")
-    idt = tbl = nl = None
+    nl = _dev(newline, "newline").to(f.dtype) if newline is not None else None
+    flags = (VT_POOL if pool else 0) | (VT_NEWLINE if newline is not None else 0)
+    return f, V, C, out, nl, flags
+
+
+def visual_tokens(feat, ids=None, table=None, newline=None, side=27, n=14, pool=True, out=None, n_points=1, pts=None, dim_t=None):
+    """K7 (+K5+K6) (+K8).  feat [V, side*side | n*n, C]; ids [V,n,n,3] int32; table Sin3DTable;
+    newline [C].  Returns / fills `out` [rows, C] (rows = V*n*(n+1) with newline else V*n*n);
+    `out` may be a row-slice view of a larger [S, C] buffer (the LLM's inputs_embeds).
+    n_points > 1 or pts given: the P-point encodings, through visual_tokens_points; the default call launches v3d_visual_tokens."""
+    if n_points > 1 or pts is not None:
+        return visual_tokens_points(feat, ids=ids, table=table, pts=pts, dim_t=dim_t, n_points=n_points, newline=newline, side=side,
+                                    n=n, pool=pool, out=out)
+    f, V, C, out, nl, flags = _token_rows(feat, newline, side, n, pool, out)
+    idt = tbl = None
     n_ids = 0
     if table is not None:
+        flags |= VT_PE
         if ids is None:
             raise V3DError("PE requested without voxel ids")
         idt = _dev(ids, "ids")
@@ -281,8 +290,6 @@ def visual_tokens(feat, ids=None, table=None, newline=None, side=27, n=14, pool=
         if table.dtype != f.dtype or table.embedding_size != C:
             raise V3DError("PE table was built for another dtype / width")
         tbl, n_ids = table.table, table.n_ids
-    if newline is not None:
-        nl = _dev(newline, "newline").to(f.dtype)
     check(lib().v3d_visual_tokens(_p(f), _p(idt), _p(tbl), n_ids, _p(nl), _p(out), out.stride(0), _code(f), V, side, n, C,
                                   flags, _stream()), "v3d_visual_tokens")
     return out
@@ -293,20 +300,11 @@ def visual_tokens_points(feat, ids=None, table=None, pts=None, dim_t=None, n_poi
     """v3d_visual_tokens_points: the fused kernel with P points per token.  Either ids [V,n,n,P,3] int32 + a Sin3DTable in the points
     layout (n_points > 1 or points_layout=True), or pts [V,n,n,P,3] in feat's dtype (+ dim_t, default the reference's) for trig on the
     fly.  Other arguments as visual_tokens."""
-    f = _dev(feat, "feat")
-    V, T, C = f.shape
     if (pts is None) == (table is None):
         raise V3DError("visual_tokens_points wants either pts (continuous) or ids + table (discrete)")
-    expect = side * side if pool else n * n
-    if T != expect:
-        raise V3DError(f"feat has {T} tokens per frame, expected {expect}")
-    rows = V * n * ((n + 1) if newline is not None else n)
-    if out is None:
-        out = torch.empty((rows, C), dtype=f.dtype, device=f.device)
-    if out.dtype != f.dtype or out.shape[0] != rows or out.shape[1] != C or out.stride(1) != 1:
-        raise V3DError(f"out must be [{rows},{C}] {f.dtype} with unit column stride")
-    flags = (VT_POOL if pool else 0) | VT_PE | (VT_NEWLINE if newline is not None else 0)
-    idt = tbl = pt = dt = nl = None
+    f, V, C, out, nl, flags = _token_rows(feat, newline, side, n, pool, out)
+    flags |= VT_PE
+    idt = tbl = pt = dt = None
     n_ids = 0
     if pts is not None:
         flags |= VT_CONTINUOUS
@@ -326,8 +324,6 @@ def visual_tokens_points(feat, ids=None, table=None, pts=None, dim_t=None, n_poi
         if not getattr(table, "points_layout", False) or table.n_points != n_points or table.dtype != f.dtype or table.embedding_size != C:
             raise V3DError("PE table was built for another dtype / width / number of points (Sin3DTable(..., n_points=P))")
         tbl, n_ids = table.table, table.n_ids
-    if newline is not None:
-        nl = _dev(newline, "newline").to(f.dtype)
     check(lib().v3d_visual_tokens_points(_p(f), _p(idt), _p(pt), _p(tbl), n_ids, _p(dt), n_points, _p(nl), _p(out), out.stride(0),
                                          _code(f), V, side, n, C, flags, _stream()), "v3d_visual_tokens_points")
     return out
@@ -378,22 +374,11 @@ def pe_mlp(x, p, want_saved=False, out=None, h_out=None):
 
 def visual_tokens_rows(feat, pe, newline=None, side=27, n=14, pool=True, out=None):
     """v3d_visual_tokens_rows: visual_tokens with the PE taken from rows pe [V*n*n, C] (row stride >= C) instead of ids + a table."""
-    f = _dev(feat, "feat")
-    V, T, C = f.shape
-    expect = side * side if pool else n * n
-    if T != expect:
-        raise V3DError(f"feat has {T} tokens per frame, expected {expect}")
+    f, V, C, out, nl, flags = _token_rows(feat, newline, side, n, pool, out)
     if not isinstance(pe, torch.Tensor) or not pe.is_cuda or pe.dtype != f.dtype or pe.dim() != 2 or pe.shape[0] != V * n * n or pe.shape[1] != C \
             or pe.stride(1) != 1:
         raise V3DError(f"pe must be a [{V * n * n},{C}] {f.dtype} device tensor with unit column stride")
-    rows = V * n * ((n + 1) if newline is not None else n)
-    if out is None:
-        out = torch.empty((rows, C), dtype=f.dtype, device=f.device)
-    if out.dtype != f.dtype or out.shape[0] != rows or out.shape[1] != C or out.stride(1) != 1:
-        raise V3DError(f"out must be [{rows},{C}] {f.dtype} with unit column stride")
-    nl = _dev(newline, "newline").to(f.dtype) if newline is not None else None
-    flags = (VT_POOL if pool else 0) | VT_PE | (VT_NEWLINE if newline is not None else 0)
-    check(lib().v3d_visual_tokens_rows(_p(f), _p(pe), pe.stride(0), _p(nl), _p(out), out.stride(0), _code(f), V, side, n, C, flags, _stream()),
+    check(lib().v3d_visual_tokens_rows(_p(f), _p(pe), pe.stride(0), _p(nl), _p(out), out.stride(0), _code(f), V, side, n, C, flags | VT_PE, _stream()),
           "v3d_visual_tokens_rows")
     return out
 
